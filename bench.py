@@ -3,28 +3,31 @@
 
 Metric: Mpixels/s of the fused crop+resize+normalize+split kernel (K1), 50 variable-size crops of a 4K
 frame -> [50,3,128,64] fp32 NCHW (BASELINE.md cfg #2b), plus the fraction of the HBM roofline the kernel
-reaches and the CPU restatement timed beside it.
+reaches (and, under --full, the CPU restatement timed beside it).
 
 A "step" = one pass of the hot path over one batch = the 50 crops of ONE frame -> one tensor.  Round 5's headline regime is the one a
 drop-in runs: STRICTLY STREAM-ORDERED TICKS -- the frames of 16 cameras (16 steps) per cvgs_execute_many call =
 ONE kernel launch on one plain stream, nothing resident between two ticks (`--submission ticks`, the default).  The descriptor queue
 (`--submission queue`: one cvgs_queue_submit per step, a resident server grid -- rounds 3 / 4's headline) and one launch per step
-(`--submission graph`) are measured beside it in every line.  Steps cycle over a rotation of resident frames whose TOUCHED set (the
+(`--submission graph`) are measured beside it under --full.  Steps cycle over a rotation of resident frames whose TOUCHED set (the
 distinct 64-byte sectors holding a tapped byte + the written tensors) is several times the 256 MiB Infinity Cache -- sized from touched
 bytes, not whole frames: round 4's 20 whole frames were 0.96 x the cache and its 0.53 turned out to be cache-assisted (the 20 / 48 / 96
 frame sweep in the line: 2.15 / 2.58 / 2.64 us per step on the queue).  Inputs (frames, crop descriptors) are resident in HBM before the
 timed region; the timed launches are replayed from HIP graphs so the host's launch rate is not what is measured (the eager call path,
 host lowering included, is reported in `stream_ordered`).
 
-Timing protocol (one clock for `value`, `ms_per_step` and `roofline.frac`; mirrors the warm-up + ITERS
+Timing protocol of the headline (one clock for `value`, `ms_per_step` and `roofline.frac`; mirrors the warm-up + ITERS
 mean/min/max protocol of the reference's tests/testsCommon.cuh:122-195):
   1. pre-roll: >= 50 ms of K1 launches regardless of --warmup (clock ramp), then the W warm-up steps;
-  2. the K steps (repeated m times: m x K a multiple of the tick and >= 256) are captured as m x K / 16 tick launches and replayed
-     R >= 50 times back to back, each replay bracketed by a pair of HIP events ON THE LAUNCH STREAM; the whole sequence sits between
-     barrier + torch.cuda.synchronize() on both sides;
-  3. per-step time = MEDIAN over the R replays of (event time / (m x K)) (p10 / p90 beside it); value = pixels per step / that time,
-     ms_per_step = that time, roofline.frac = algorithmic bytes per step / that time / 8 TB/s.  The wall clock of the bracketed region
-     is reported too (`wall_ms_per_step`).
+  2. exactly K = --steps steps are timed: K / 16 tick launches, replayed from HIP graphs of whole rotations (a K that is not a whole
+     number of ticks ends in one partial tick), a HIP event ON THE LAUNCH STREAM at every replay boundary, torch.cuda.synchronize()
+     on both sides;
+  3. per-step time = event time from the first boundary to the last / K; value = pixels per step / that time, ms_per_step = that
+     time, roofline.frac = algorithmic bytes per step / that time / 8 TB/s.  The spread over the replays and the wall clock of the
+     timed region are reported too.
+A plain run does nothing else.  --full adds what the line carries beside the headline: the copy ceiling, the residency sweep, the
+other submission regimes (each on its own replay protocol), the CPU baselines, the extra sweeps and the perf gate.
+--dump-outputs DIR writes the tensor the last timed step computed to DIR/output.npy.
 
 N > 1 (one process per GPU, torch.distributed/RCCL) runs BASELINE cfg #5: each rank owns one resident 6K frame stream
 and 64 crops per step (weak scaling), K1 writes the rank's rows of the [N*64,3,128,64] tensor, and the tensor is
@@ -71,8 +74,13 @@ def baseline_metric():
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=256)
+    p.add_argument("--steps", type=int, default=256, help="timed steps (frames) of the headline; the --full legs time min(steps, 256)-step sequences")
     p.add_argument("--warmup", type=int, default=64)
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline: copy ceiling, residency sweep, the other submission regimes, CPU baselines, extra sweeps and the perf gate "
+                        "(the --no-* options below switch parts of it off)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the tensor the last timed step computed to DIR/output.npy (float32, [crops,3,128,64])")
     p.add_argument("--crops", type=int, default=CROPS, help="crops per launch (headline: 50)")
     p.add_argument("--frames", type=int, default=0, help="distinct resident frames (0 = enough to defeat the cache)")
     p.add_argument("--frames-per-launch", type=int, default=1, help="independent 50-crop chains fused per launch (cvgs_execute_many)")
@@ -320,9 +328,17 @@ def measure_queue(wl, steps, warmup, barrier=lambda: None, target_s=0.25, min_re
                 "queue": {"worker_workgroups": st["workgroups"], "ring_slots": st["ring_slots"],
                           "host_writes_device_memory": st["host_writes_device_memory"], "error": st["error"]},
                 "latency": {"median_us": round(float(np.median(lat)), 3), "p10_us": round(percentile(lat, 0.1), 3),
-                            "p90_us": round(percentile(lat, 0.9), 3)}}
+                            "p90_us": round(percentile(lat, 0.9), 3)},
+                "last_frame": (n - 1) % len(wl.chains)}
     finally:
         q.destroy()
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each array as d/<name>.npy in float32 (what a caller of the timed path receives, for output-for-output comparisons)."""
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def queue_outputs_match_execute(wl):
@@ -544,6 +560,77 @@ def measure_ticks(wl, steps, warmup, barrier=lambda: None, eager=False, target_s
     return out
 
 
+CHUNK_LAUNCHES = 96  # launches per graph replay of the headline's timed region (rounded to whole rotations)
+
+
+def measure_steps(wl, steps, warmup, eager=False):
+    """The headline's timed region: exactly `steps` steps (frames), wl.per_launch of them per launch.  Whole launches cycle over the
+    rotation as replays of a graph of whole rotations (each replay continues the rotation where the last one stopped); a step count that
+    is not a whole number of ticks ends in one partial tick over the frames that follow.  HIP events on the launch stream at every
+    replay boundary; per-step time = event time from the first boundary to the last / steps.  Returns measure()'s keys, `launch_s`,
+    the launches per replay and `last_frame` (the rotation index of the frame the last step wrote)."""
+    s = torch.cuda.current_stream().cuda_stream
+    M = wl.per_launch
+    rotation = len(wl.groups) if M > 1 else len(wl.chains)
+    full, rest = divmod(steps, M)
+    chunk = rotation * max(1, CHUNK_LAUNCHES // rotation)
+    n_chunks, tail_full = divmod(full, chunk)
+    tail_pack = cvgs.pack_chains(wl.chains[(tail_full % rotation) * M:][:rest]) if rest else None
+
+    def run_chunk(stream):
+        for i in range(chunk):
+            wl.launch(i, stream)
+
+    def run_tail(stream):  # the launch index restarts at 0: n_chunks x chunk is a whole number of rotations
+        for i in range(tail_full):
+            wl.launch(i, stream)
+        if rest:
+            capi.check(wl.lib.cvgs_execute_many(tail_pack, rest, stream))
+
+    units = {}
+    for name, fn, launches in (("chunk", run_chunk, chunk if n_chunks else 0), ("tail", run_tail, tail_full + (1 if rest else 0))):
+        if not launches:
+            continue
+        if eager:
+            units[name] = (lambda fn=fn: fn(s)), launches
+        else:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                fn(torch.cuda.current_stream().cuda_stream)
+            units[name] = g.replay, launches
+    # 1. every graph once (instantiates / uploads it before any clock starts), pre-roll (clock ramp), the W warm-up steps
+    for u, _ in units.values():
+        u()
+    torch.cuda.synchronize()
+    first, first_launches = next(iter(units.values()))
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < PREROLL_S:
+        for _ in range(max(1, 64 // first_launches)):
+            first()
+        torch.cuda.synchronize()
+    for i in range(max(1, -(-warmup // M))):
+        wl.launch(i, s)
+    torch.cuda.synchronize()
+    # 2. the timed region: n_chunks replays of the rotation graph, then the tail, an event at every boundary
+    order = ([units["chunk"][0]] * n_chunks if n_chunks else []) + ([units["tail"][0]] if "tail" in units else [])
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(order) + 1)]
+    w0 = time.perf_counter()
+    ev[0].record()
+    for u, e in zip(order, ev[1:]):
+        u()
+        e.record()
+    torch.cuda.synchronize()
+    w1 = time.perf_counter()
+    step_s = ev[0].elapsed_time(ev[-1]) * 1e-3 / steps
+    t = np.sort(np.array([ev[i].elapsed_time(ev[i + 1]) * 1e-3 / (chunk * M) for i in range(n_chunks)] or [step_s]))
+    return {"step_s": step_s, "median_s": float(np.median(t)), "p10_s": percentile(t, 0.10), "p90_s": percentile(t, 0.90), "min_s": float(t[0]), "wall_s": w1 - w0,
+            "replays": len(order), "passes_per_replay": 1, "wall_step_s": (w1 - w0) / steps, "launch_s": step_s * M,
+            "launches_per_replay": chunk if n_chunks else units["tail"][1], "launches": full + (1 if rest else 0), "tick": M,
+            "graphs": "%d replay(s) of a graph of %d launches (whole rotations)%s" % (n_chunks, chunk, ", then one graph of the %d launches left" % units["tail"][1]
+                                                                                      if "tail" in units else ""),
+            "last_frame": (steps - 1) % (rotation * M)}
+
+
 def ticks_match_single_launches(wl, single):
     """Every resident frame's tensor as the tick launches left it against what ONE cvgs_execute launch writes for the same chain (`single`:
     a Workload over the same frames and crop lists with its own tensors, one chain per launch)."""
@@ -561,6 +648,9 @@ def ticks_match_single_launches(wl, single):
 
 def main():
     a = parse()
+    if a.steps < 1 or (a.dump_outputs and (a.gpus > 1 or a.force_dist)):
+        write_line(error_line(a, "--steps must be >= 1" if a.steps < 1 else "--dump-outputs: single-GPU runs only"))
+        raise SystemExit(2)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -610,19 +700,22 @@ def main():
             if m["server_launches_in_timed_region"] == 1:
                 break
         m["attempts_server_launches"] = attempts
-        queue_ok = queue_outputs_match_execute(wl)
-    elif use_ticks:
-        m = measure_ticks(wl, a.steps, a.warmup, eager=a.eager)
     else:
-        m = measure(wl, a.steps, a.warmup, eager=a.eager)
+        m = measure_steps(wl, a.steps, a.warmup, eager=a.eager)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"output": wl.outs[m["last_frame"]].view(n, 3, W.DST[1], W.DST[0])})
+    if use_queue and a.full:
+        queue_ok = queue_outputs_match_execute(wl)
     step_s = m["step_s"]
     px_per_step = n * W.DST[0] * W.DST[1]
+    steps_protocol = ("pre-roll >= %d ms, the W warm-up steps; then exactly K steps: %s; HIP events on the launch stream at every replay boundary; "
+                      "per-step time = event time from the first boundary to the last / K" % (
+                          int(PREROLL_S * 1e3), "eager launches" if a.eager else m.get("graphs")))
     if use_ticks:
         submission = ("strictly stream-ordered TICKS: %d steps (frames, one 50-crop chain each) per cvgs_execute_many call = ONE kernel launch (grid z = chain) on "
                       "one plain stream, nothing resident between ticks; device plane tables, %s" % (M, "eager" if a.eager else "HIP-graph replay"))
         regime = "%d independent 50-crop chains per launch: a tick of %d cameras' frames" % (M, M)
-        protocol = ("pre-roll >= %d ms; the K steps repeated m times (m x K a whole number of ticks, >= 256 steps) = m x K / %d tick launches per graph replay, "
-                    "R replays back to back, HIP events on the launch stream around each; per-step time = median over replays of event time / (m x K)" % (int(PREROLL_S * 1e3), M))
+        protocol = steps_protocol + " (K / %d tick launches; a K that is not a whole number of ticks ends in one partial tick)" % M
     elif use_queue:
         submission = "device-side descriptor queue: one cvgs_queue_submit per step, a resident server grid, no launch per step"
         regime = "one frame (50 crops) per step; consecutive steps overlap on the device (batch k+1 loads while batch k stores)"
@@ -630,11 +723,10 @@ def main():
                     "pipelined one ahead, host wall clock stamped at every awaited last ticket; per-step time = median over "
                     "replays of stamp difference / (m x K) -- end to end, host side included" % int(PREROLL_S * 1e3))
     else:
-        submission = "eager" if a.eager else "hipGraph replay (%d-launch graphs)" % (256 if a.steps >= 256 else a.steps * -(-256 // a.steps))
+        submission = "eager" if a.eager else "hipGraph replay (%d-launch graphs)" % m["launches_per_replay"]
         regime = ("one launch per step, steps serialised on one stream (launch-latency regime: a 50-crop launch moves ~9 MB = 1.1 us at 8 TB/s "
                   "behind a ~1.8 us launch/drain floor)")
-        protocol = ("pre-roll >= %d ms; graph of the K steps (repeated m times when K < 256, so that a graph holds >= 256 launches) replayed R times back to "
-                    "back, HIP events on the launch stream around each replay; per-step time = median over replays of event time / (m x K)" % int(PREROLL_S * 1e3))
+        protocol = steps_protocol
     result = {
         "metric": baseline_metric(),
         "value": round(px_per_step / step_s / 1e6, 1),
@@ -663,7 +755,12 @@ def main():
                    "step_us_p90": round(m["p90_s"] * 1e6, 4), "step_us_min": round(m["min_s"] * 1e6, 4),
                    "wall_ms_per_step": round(m["wall_step_s"] * 1e3, 6),
                    "wall_note": "wall clock of the whole barrier+synchronize bracketed region / ((R+1) x K): includes R graph "
-                                "submissions and event records"},
+                                "submissions and event records"} if use_queue else
+                  {"protocol": protocol, "steps_timed": a.steps, "replays": m["replays"], "step_us_mean": round(step_s * 1e6, 4),
+                   "step_us_median": round(m["median_s"] * 1e6, 4), "step_us_p10": round(m["p10_s"] * 1e6, 4), "step_us_p90": round(m["p90_s"] * 1e6, 4),
+                   "step_us_min": round(m["min_s"] * 1e6, 4),
+                   "spread": "median / p10 / p90 / min: per-step time of each whole-rotation graph replay (the mean when the K steps hold none)",
+                   "wall_ms_per_step": round(m["wall_step_s"] * 1e3, 6), "wall_note": "wall clock of the timed region / K: includes the submissions and event records"},
     }
 
     alg = float(np.mean([W.k1_algorithmic_bytes(c) for c in wl.crops]))  # per step (one frame's 50 crops)
@@ -671,7 +768,7 @@ def main():
     kernel_us = step_s * 1e6 * M  # per launch
     if use_ticks:
         result["timing"]["tick_launch"] = {"us_per_launch": round(m["launch_s"] * 1e6, 3), "launches_per_replay": m["launches_per_replay"], "steps_per_launch": M,
-                                           "clock": "HIP events on the launch stream around each replay / launches per replay (includes the ~1.5 us boundary between two launches)",
+                                           "clock": "the headline's per-step time x steps per launch (includes the ~1.5 us boundary between two launches)",
                                            "kernel": wl.kernel + " (K1's fused form: k1_resize_split<3, 0, 2, ...>, planes in device tables, blockIdx.z = chain)"}
     if use_queue:
         # the dominant kernel is the server grid: ONE launch served every batch of the timed region; its duration between two
@@ -685,7 +782,8 @@ def main():
         result["queue"]["every_frame_bit_identical_to_cvgs_execute"] = queue_ok
     units = 1 if use_queue else M  # steps one "launch" of the dominant kernel serves (the queue: one batch of its ONE server call)
     achieved = alg * units / (kernel_us * 1e-6) / 1e9
-    ceiling = copy_ceiling(dev)
+    ceiling = copy_ceiling(dev) if a.full else None
+    k = min(a.steps, 256)  # the K of the --full legs' own protocol (measure / measure_ticks / measure_queue)
     result["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                           "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": pmc_traffic(n, a.table, M, use_queue),
                           "kernel": "k1q_server (queue) / " + wl.kernel if use_queue else wl.kernel, "kernel_us": round(kernel_us, 3), "steps_per_launch": units,
@@ -707,23 +805,21 @@ def main():
         sk = skeleton_evidence(M)
         if sk:
             result["roofline"]["skeleton"] = sk
-    if not a.frames and not a.no_sweep and not a.eager and (use_queue or (use_ticks and M == TICK)):
+    if a.full and not a.frames and not a.no_sweep and not a.eager and (use_queue or (use_ticks and M == TICK)):
         # the same step on smaller rotations: does the figure depend on what the Infinity Cache can hold?
         sweep = {}
-        for k in (RESIDENCY_SWEEP if use_queue else TICK_SWEEP):
-            if k == n_frames:
-                sweep[str(k)] = round(step_s * 1e6, 4)
-            elif k < n_frames and use_queue:
-                sweep[str(k)] = round(measure_queue(RotationView(wl, k), a.steps, 0, target_s=0.08, min_replays=12, events=False)["step_s"] * 1e6, 4)
-            elif k < n_frames:
-                sweep[str(k)] = round(measure_ticks(RotationView(wl, k), a.steps, 0, target_s=0.08, min_replays=12)["step_s"] * 1e6, 4)
+        for r in (RESIDENCY_SWEEP if use_queue else TICK_SWEEP):  # every point on the legs' protocol (the headline's K may be short)
+            if r <= n_frames and use_queue:
+                sweep[str(r)] = round(measure_queue(RotationView(wl, r), k, 0, target_s=0.08, min_replays=12, events=False)["step_s"] * 1e6, 4)
+            elif r <= n_frames:
+                sweep[str(r)] = round(measure_ticks(RotationView(wl, r), k, 0, target_s=0.08, min_replays=12)["step_s"] * 1e6, 4)
         result["roofline"]["sweep_us"] = sweep
     single = None
-    if use_ticks and M == TICK and not a.eager and not a.headline_only:
+    if a.full and use_ticks and M == TICK and not a.eager and not a.headline_only:
         # the same frames and crop lists, one chain per launch / per queue submit (their own tensors): the other two regimes, and the check
         single = Workload(dev, n_frames, n, rank, world, False, share=wl)
         result["ticks_ok"] = ticks_match_single_launches(wl, single)
-        mg = measure(single, a.steps, a.warmup, target_s=0.12)
+        mg = measure(single, k, a.warmup, target_s=0.12)
         result["one_launch_per_step"] = {"us_per_step": round(mg["step_s"] * 1e6, 4), "Mpix_per_s": round(px_per_step / mg["step_s"] / 1e6, 1),
                                          "frac": round(alg / mg["step_s"] / 1e9 / HBM_PEAK_GBS, 4), "kernel": single.kernel,
                                          "submission": "hipGraph replay, one cvgs_execute launch per step"}
@@ -748,7 +844,7 @@ def main():
         # construction, the launch is write-bound)
         try:
             wla = Workload(dev, n_frames, n, rank, world, True, per_launch=M, share=wl, fixed=True)
-            ma = measure_ticks(wla, a.steps, 0, target_s=0.1, min_replays=12)
+            ma = measure_ticks(wla, k, 0, target_s=0.1, min_replays=12)
             alg_a = wla.algorithmic_bytes() / M
             result["cfg2a"] = {"us_per_step": round(ma["step_s"] * 1e6, 4), "frac": round(alg_a / ma["step_s"] / 1e9 / HBM_PEAK_GBS, 4),
                                "Mpix_per_s": round(px_per_step / ma["step_s"] / 1e6, 1), "algorithmic_bytes_per_step": int(alg_a),
@@ -761,13 +857,13 @@ def main():
         if not a.no_queue_leg and n <= 74:
             # the descriptor queue (rounds 3 / 4's headline; an OPT-IN since round 5: a resident server costs a co-resident GEMM x1.6, `coexistence`):
             # one cvgs_queue_submit per step on the same rotation, and on the rotations round 4 used
-            mq = measure_queue(single, a.steps, a.warmup, target_s=0.12, events=False)
+            mq = measure_queue(single, k, a.warmup, target_s=0.12, events=False)
             qk = {"us_per_step": round(mq["step_s"] * 1e6, 4), "frac": round(alg / mq["step_s"] / 1e9 / HBM_PEAK_GBS, 4),
                   "latency_us": mq["latency"]["median_us"], "ok": bool(queue_outputs_match_execute(single)) and not mq["queue"]["error"]}
             if not a.frames and not a.no_sweep:
-                qk["sweep_us"] = {str(k): (qk["us_per_step"] if k == n_frames else
-                                           round(measure_queue(RotationView(single, k), a.steps, 0, target_s=0.08, min_replays=12, events=False)["step_s"] * 1e6, 4))
-                                  for k in RESIDENCY_SWEEP if k <= n_frames}
+                qk["sweep_us"] = {str(r): (qk["us_per_step"] if r == n_frames else
+                                           round(measure_queue(RotationView(single, r), k, 0, target_s=0.08, min_replays=12, events=False)["step_s"] * 1e6, 4))
+                                  for r in RESIDENCY_SWEEP if r <= n_frames}
             result["queue_opt_in"] = qk
         for big in (64,):  # larger ticks on the same rotation (needs a multiple of the tick: 128 frames)
             try:
@@ -778,15 +874,15 @@ def main():
                 torch.cuda.empty_cache()
             except Exception as ex:
                 result["tick%d_error" % big] = repr(ex)[:120]
-    elif use_queue:
+    elif a.full and use_queue:
         result["timing"]["single_launch_latency"] = single_launch_latency(wl)
-        mg = measure(wl, a.steps, a.warmup)
+        mg = measure(wl, k, a.warmup)
         result["one_launch_per_step"] = {"us_per_step": round(mg["step_s"] * 1e6, 4), "Mpix_per_s": round(px_per_step / mg["step_s"] / 1e6, 1),
                                          "frac": round(alg / mg["step_s"] / 1e9 / HBM_PEAK_GBS, 4), "kernel": wl.kernel,
                                          "submission": "hipGraph replay, one cvgs_execute launch per step"}
-    if not a.no_cpu and (M == 1 or M == TICK):
+    if a.full and not a.no_cpu and (M == 1 or M == TICK):
         result["cpu_baseline"] = cpu_baseline(single if single is not None else wl, a.cpu_seconds)
-    if (use_queue or (use_ticks and M == TICK)) and not a.no_regimes and not a.eager:
+    if a.full and (use_queue or (use_ticks and M == TICK)) and not a.no_regimes and not a.eager:
         # the regimes beside the headline: stream-ordered submission EAGER with a producer on the stream (the reference's call shape; ticks as one
         # launch, the queue's gates), batch latency by queue depth, and coexistence with a consumer on the same GPU (tools/bench_queue_regimes.py)
         # In a FRESH process: what these legs measure is paced by the runtime's stream scheduling, and inside this process -- after the
@@ -811,10 +907,10 @@ def main():
     if single is not None:
         del single
         torch.cuda.empty_cache()
-    if not a.no_extra:
+    if a.full and not a.no_extra:
         result["extra"] = extra_sweeps(dev, a)
     cfgs = configs_block(result.get("extra", {}))
-    if not a.no_cpu:
+    if a.full and not a.no_cpu:
         try:
             cfgs["cfg1_cpu"] = cfg1_cpu()
         except Exception as ex:

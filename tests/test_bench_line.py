@@ -93,3 +93,79 @@ def test_gpus_n_without_the_gpus_prints_a_parseable_error_line():
     assert p.returncode != 0
     j = _check(p.stdout.strip().splitlines()[-1])
     assert j["value"] is None and j["n_gpus"] == 8 and "visible GPU" in j["error"]
+
+
+class _FakeEvent:
+    """torch.cuda.Event stand-in: remembers how many frames the fake workload had processed when it was recorded; 1 ms per frame."""
+    log = None
+
+    def __init__(self, **_):
+        self.at = None
+
+    def record(self, *_):
+        self.at = len(_FakeEvent.log)
+
+    def elapsed_time(self, other):
+        return float(other.at - self.at)
+
+
+class _FakeWorkload:
+    """Workload's launch interface over a rotation of `frames` frames, `per_launch` per launch; every launch logs the frames it processed."""
+
+    def __init__(self, frames, per_launch, log):
+        self.per_launch, self.log = per_launch, log
+        self.chains = list(range(frames))
+        self.groups = [self.chains[g:g + per_launch] for g in range(0, frames, per_launch)] if per_launch > 1 else []
+        wl = self
+
+        class Lib:
+            def cvgs_execute_many(self, arr, n, stream):
+                assert len(arr) == n
+                wl.log.extend(arr)
+                return 0
+        self.lib = Lib()
+
+    def launch(self, i, stream):
+        self.log.extend(self.groups[i % len(self.groups)] if self.per_launch > 1 else [self.chains[i % len(self.chains)]])
+
+
+@pytest.mark.parametrize("frames,per_launch,steps", [(96, 16, 1), (96, 16, 20), (96, 16, 256), (96, 16, 1536 * 2 + 17), (16, 16, 100),
+                                                     (24, 1, 1), (24, 1, 250)])
+def test_measure_steps_times_exactly_the_requested_steps(monkeypatch, frames, per_launch, steps):
+    """--steps K: the timed region (first event to last) processes exactly K frames, in rotation order from frame 0, partial tick included;
+    ms_per_step is that region's time / K; `last_frame` is the frame of the K-th step (what --dump-outputs writes)."""
+    log = []
+    _FakeEvent.log = log
+    monkeypatch.setattr(bench.torch.cuda, "Event", _FakeEvent)
+    monkeypatch.setattr(bench.torch.cuda, "synchronize", lambda *_: None)
+    monkeypatch.setattr(bench.torch.cuda, "current_stream", lambda *_: type("S", (), {"cuda_stream": 0})())
+    monkeypatch.setattr(bench.cvgs, "pack_chains", lambda chains: list(chains))
+    monkeypatch.setattr(bench, "PREROLL_S", 0.0)
+    wl = _FakeWorkload(frames, per_launch, log)
+    starts = []
+    real_record = _FakeEvent.record
+
+    def record(self, *a):
+        real_record(self, *a)
+        starts.append(self.at)
+    monkeypatch.setattr(_FakeEvent, "record", record)
+    m = bench.measure_steps(wl, steps, 5, eager=True)
+    timed = log[starts[0]:starts[-1]]
+    assert timed == [s % frames for s in range(steps)]
+    assert m["step_s"] == pytest.approx(1e-3)
+    assert m["last_frame"] == (steps - 1) % frames == timed[-1]
+    assert m["launches"] == -(-steps // per_launch)
+
+
+def test_plain_run_is_lean_by_default():
+    """The plain command line carries no --full (the secondary legs) and no output dump unless asked for."""
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        a = bench.parse()
+        assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "out"]
+        a = bench.parse()
+        assert a.full and a.dump_outputs == "out"
+    finally:
+        sys.argv = argv

@@ -45,9 +45,9 @@ def brief(j):
 b_prof, b_un, b_205, b_m16p, b_m16 = (jline(n) for n in ("bench_trace.json", "bench_unprofiled.json", "bench_unprofiled_20_5.json",
                                                            "bench_trace_m16.json", "bench_unprofiled_m16.json"))
 with open(os.path.join(P, label + "_k1_bench_kernel_stats.txt"), "w") as f:
-    f.write("# %s: rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --no-cpu --no-extra\n" % label)
+    f.write("# %s: rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --no-cpu --no-extra\n" % label)
     f.write("# bench line of the SAME (profiled) run:   %s\n" % brief(b_prof))
-    f.write("# un-profiled `python bench.py` (same box):  %s\n" % brief(b_un))
+    f.write("# un-profiled `python bench.py --full --no-cpu --no-extra` (same box):  %s\n" % brief(b_un))
     f.write("# un-profiled driver command (--steps 20 --warmup 5): %s\n" % brief(b_205))
     f.write("# (profiled passes run 10-15 % slower: profiler serialisation + lower clocks, MI355X_MICROARCH.md DVFS note)\n")
     f.write("# rocprofv3's own kernel stats (first rows):\n")
@@ -55,7 +55,7 @@ with open(os.path.join(P, label + "_k1_bench_kernel_stats.txt"), "w") as f:
     f.write("\n" + cut(rd("bench_trace_kernels.txt")))
 with open(os.path.join(P, label + "_k1_m16_kernel_stats.txt"), "w") as f:
     f.write("# %s: 16 independent 50-crop chains per launch (cvgs_execute_many): rocprofv3 --kernel-trace --stats -- python bench.py "
-            "--frames-per-launch 16 --no-cpu --no-extra\n" % label)
+            "--full --frames-per-launch 16 --no-cpu --no-extra\n" % label)
     f.write("# bench line of the profiled run: %s\n# un-profiled:                     %s\n" % (brief(b_m16p), brief(b_m16)))
     f.write("\n" + cut(rd("bench_trace_m16_kernels.txt")))
 with open(os.path.join(P, label + "_cfg3_cfg4_kernel_stats.txt"), "w") as f:
@@ -67,10 +67,10 @@ with open(os.path.join(P, label + "_cfg3_cfg4_kernel_stats.txt"), "w") as f:
     f.write("\n" + cut(rd("cvtcolor_trace_kernels.txt")))
 with open(os.path.join(P, label + "_bench_lines.txt"), "w") as f:
     f.write("# %s: raw bench.py output lines, un-profiled, one MI355X box\n" % label)
-    f.write("## python bench.py --gpus 1 --steps 20 --warmup 5   (the driver's command; with the CPU baseline and every extra sweep)\n")
+    f.write("## python bench.py --full --gpus 1 --steps 20 --warmup 5   (with the CPU baseline and every extra sweep)\n")
     f.write(rd("bench_unprofiled_20_5.json"))
-    f.write("## python bench.py --no-cpu --no-extra\n" + rd("bench_unprofiled.json"))
-    f.write("## python bench.py --frames-per-launch 16 --no-cpu --no-extra\n" + rd("bench_unprofiled_m16.json"))
+    f.write("## python bench.py --full --no-cpu --no-extra\n" + rd("bench_unprofiled.json"))
+    f.write("## python bench.py --full --frames-per-launch 16 --no-cpu --no-extra\n" + rd("bench_unprofiled_m16.json"))
 
 k = {n: (pmc_value("pmc_FETCH_SIZE_%s.txt" % n, "FETCH_SIZE"), pmc_value("pmc_WRITE_SIZE_%s.txt" % n, "WRITE_SIZE")) for n in ("50", "m16", "3200")}
 calA, calB, calC = (pmc_value("calib_FETCH_SIZE_%s.txt" % x, "FETCH_SIZE") for x in "ABC")

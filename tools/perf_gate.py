@@ -73,7 +73,7 @@ def check(rows, table=None):
 def headline_rows():
     """the headline on bench.py's own clocks: the queue (one submit per step), one graph-replayed launch per step, the stream-ordered ticks"""
     import subprocess
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu", "--no-extra", "--no-regimes"], capture_output=True, text=True)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu", "--no-extra", "--no-regimes"], capture_output=True, text=True)
     rows = []
     try:
         j = json.load(open(os.path.join(ROOT, "bench_extra.json")))

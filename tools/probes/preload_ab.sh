@@ -1,5 +1,5 @@
 # kernel-argument preload of K1's leading scalars: the launch-bound regimes (run on the GPU box; compare trees / PRELOAD= builds)
-python bench.py --no-cpu --no-extra --no-regimes --no-sweep --no-queue-leg 2>/dev/null | python -c "
+python bench.py --full --no-cpu --no-extra --no-regimes --no-sweep --no-queue-leg 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('ticks16 graph us/frame', d['ms_per_step']*1e3, 'one_launch graph', d.get('one_launch_per_step'), 'lat', d.get('latency_us'), 'tick64', d.get('tick64_us_per_step'))"

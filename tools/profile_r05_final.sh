@@ -10,11 +10,11 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 RP="rocprofv3 --kernel-trace --output-format csv"
 SUM="python tools/prof_summary.py"
 python -m pytest tests -m gpu -x -q 2>&1 | grep -E "passed|failed|error" | tail -3 > $OUT/pytest_gpu_tail.txt
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_20_5.json 2> /dev/null
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_20_5.json 2> /dev/null
 cp bench_extra.json $OUT/bench_20_5_extra.json 2> /dev/null
-python bench.py > $OUT/bench_default.json 2> /dev/null
+python bench.py --full > $OUT/bench_default.json 2> /dev/null
 python bench.py --gpus 1 --force-dist --steps 20 --warmup 5 --no-extra > $OUT/bench_force_dist.json 2> /dev/null
-python bench.py --submission queue --no-extra --no-regimes > $OUT/bench_submission_queue.json 2> /dev/null
+python bench.py --full --submission queue --no-extra --no-regimes > $OUT/bench_submission_queue.json 2> /dev/null
 # kernel trace of the headline command: the fused K1 launch's average duration against timing.tick_launch.us_per_launch of the same run
 timeout -k 5 300 $RP --stats -d $RAW/bench_trace -o t -- python bench.py --no-cpu --no-extra --no-regimes --no-sweep --headline-only > $OUT/bench_trace.json 2> /dev/null
 $SUM kernels $RAW/bench_trace/t_kernel_trace.csv > $OUT/bench_trace_kernels.txt 2>&1

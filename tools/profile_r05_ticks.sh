@@ -9,10 +9,10 @@ mkdir -p $OUT $RAW
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 RP="rocprofv3 --kernel-trace --output-format csv"
 SUM="python tools/prof_summary.py"
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_20_5.json 2> $OUT/bench_20_5.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_20_5.json 2> $OUT/bench_20_5.err
 cp bench_extra.json $OUT/bench_20_5_extra.json 2> /dev/null
 tail -c 3000 $OUT/bench_20_5.err > $OUT/bench_20_5.err.tail; rm -f $OUT/bench_20_5.err
-python bench.py --no-extra > $OUT/bench_default_no_extra.json 2> /dev/null
+python bench.py --full --no-extra > $OUT/bench_default_no_extra.json 2> /dev/null
 # kernel trace of the headline command (no side legs): the fused K1 launch's average duration must agree with timing.tick_launch.us_per_launch
 timeout -k 5 300 $RP --stats -d $RAW/bench_trace -o t -- python bench.py --no-cpu --no-extra --no-regimes --no-sweep --headline-only > $OUT/bench_trace.json 2> /dev/null
 $SUM kernels $RAW/bench_trace/t_kernel_trace.csv > $OUT/bench_trace_kernels.txt 2>&1

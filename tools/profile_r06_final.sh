@@ -11,9 +11,9 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 RP="rocprofv3 --kernel-trace --output-format csv"
 SUM="python tools/prof_summary.py"
 python -m pytest tests -m gpu -x -q 2>&1 | grep -E "passed|failed|error" | tail -3 > $OUT/pytest_gpu_tail.txt
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_20_5.json 2> /dev/null
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_20_5.json 2> /dev/null
 cp bench_extra.json $OUT/bench_20_5_extra.json 2> /dev/null
-python bench.py > $OUT/bench_default.json 2> /dev/null
+python bench.py --full > $OUT/bench_default.json 2> /dev/null
 python bench.py --gpus 1 --force-dist --steps 20 --warmup 5 --no-extra > $OUT/bench_force_dist.json 2> /dev/null
 CVGS_BENCH_WORLD_ON_ONE_GPU=1 python bench.py --gpus 2 --steps 20 --warmup 5 --no-extra > $OUT/bench_gpus2_on_one_gpu.json 2> /dev/null
 # kernel trace of the headline command: the fused K1 launch's average duration against timing.tick_launch.us_per_launch of the same run

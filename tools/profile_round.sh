@@ -14,14 +14,14 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 RP="rocprofv3 --kernel-trace --output-format csv"
 SUM="python tools/prof_summary.py"
 # 0. the un-profiled headline lines (driver's command and the default)
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_unprofiled_20_5.json 2>/dev/null
-python bench.py --no-cpu --no-extra > $OUT/bench_unprofiled.json 2>/dev/null
-python bench.py --frames-per-launch 16 --no-cpu --no-extra > $OUT/bench_unprofiled_m16.json 2>/dev/null
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_unprofiled_20_5.json 2>/dev/null
+python bench.py --full --no-cpu --no-extra > $OUT/bench_unprofiled.json 2>/dev/null
+python bench.py --full --frames-per-launch 16 --no-cpu --no-extra > $OUT/bench_unprofiled_m16.json 2>/dev/null
 # 1. the headline bench command, kernel trace + stats; the same with 16 frames fused per launch
-timeout -k 5 240 $RP --stats -d $RAW/bench_trace -o t -- python bench.py --no-cpu --no-extra > $OUT/bench_trace.json 2> $OUT/bench_trace.err
+timeout -k 5 240 $RP --stats -d $RAW/bench_trace -o t -- python bench.py --full --no-cpu --no-extra > $OUT/bench_trace.json 2> $OUT/bench_trace.err
 $SUM kernels $RAW/bench_trace/t_kernel_trace.csv > $OUT/bench_trace_kernels.txt 2>&1
 head -6 $RAW/bench_trace/t_kernel_stats.csv > $OUT/bench_trace_stats_head.txt 2>/dev/null
-timeout -k 5 240 $RP --stats -d $RAW/bench_trace_m16 -o t -- python bench.py --frames-per-launch 16 --no-cpu --no-extra > $OUT/bench_trace_m16.json 2>/dev/null
+timeout -k 5 240 $RP --stats -d $RAW/bench_trace_m16 -o t -- python bench.py --full --frames-per-launch 16 --no-cpu --no-extra > $OUT/bench_trace_m16.json 2>/dev/null
 $SUM kernels $RAW/bench_trace_m16/t_kernel_trace.csv > $OUT/bench_trace_m16_kernels.txt 2>&1
 # 2. HBM counters (eager, fewer steps: counters serialise the kernels)
 for C in FETCH_SIZE WRITE_SIZE; do

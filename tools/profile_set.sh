@@ -9,9 +9,9 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 python -m pytest tests -m gpu -x -q 2>&1 | grep -E "passed|failed|error" | tail -3 > $OUT/pytest_gpu_tail.txt
 bash tools/profile_queue.sh $TAG > /dev/null 2>&1
-python bench.py > $OUT/bench_default.json 2> /dev/null
+python bench.py --full > $OUT/bench_default.json 2> /dev/null
 cp bench_extra.json $OUT/bench_default_extra.json 2> /dev/null
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_20_5.json 2> /dev/null
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_20_5.json 2> /dev/null
 cp bench_extra.json $OUT/bench_20_5_extra.json 2> /dev/null
 python bench.py --gpus 1 --force-dist --steps 20 --warmup 5 --no-extra > $OUT/bench_force_dist.json 2> /dev/null
 bash tools/profile_queue_sustained.sh $TAG > /dev/null 2>&1

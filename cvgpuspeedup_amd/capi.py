@@ -24,6 +24,9 @@ OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_HIP, ERR_NO_DEVICE, ERR_RCCL = 0, -1, -2, 
 CIRCULAR_MIRRORED = 1
 CIRCULAR_CAPTURABLE = 2
 DEPTH_8U, DEPTH_8S, DEPTH_16U, DEPTH_16S, DEPTH_32S, DEPTH_32F, DEPTH_64F, DEPTH_16F = range(8)
+# CV_16BF (bfloat16): depth 16F plus a flag bit outside OpenCV's 12-bit type mask; also a CAST / CAST_TRUNC aux
+TYPE_FLAG_BF16 = 0x1000
+DEPTH_16BF = DEPTH_16F | TYPE_FLAG_BF16
 
 
 def make_type(depth, cn):
@@ -36,6 +39,15 @@ def type_depth(t):
 
 def type_cn(t):
     return ((t >> 3) & 63) + 1
+
+
+def type_is_bf16(t):
+    return (t & TYPE_FLAG_BF16) != 0
+
+
+def cast_aux(t):
+    """The aux of a CAST / CAST_TRUNC stage that produces type t (CV_16BF types: DEPTH_16BF)."""
+    return DEPTH_16BF if type_depth(t) == DEPTH_16F and type_is_bf16(t) else type_depth(t)
 
 
 # read kinds

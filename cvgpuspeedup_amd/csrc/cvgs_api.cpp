@@ -11,6 +11,7 @@
 #include <cstring>
 #include <mutex>
 #include <new>
+#include <set>
 #include <string>
 #include <utility>
 #include <thread>
@@ -19,6 +20,16 @@
 #include "cvgs_device.h"
 
 using namespace cvgs;
+
+const char* cvgs::bf16_kernel_name(const char* f16_name) {
+    static std::mutex m;
+    static std::set<std::string> names;
+    std::string n(f16_name);
+    const size_t at = n.rfind("f16");
+    n = at == std::string::npos ? n + "_bf16" : n.substr(0, at) + "bf16" + n.substr(at + 3);
+    std::lock_guard<std::mutex> lk(m);
+    return names.insert(n).first->c_str();
+}
 
 
 namespace {
@@ -37,11 +48,22 @@ int hip_fail(hipError_t e, const char* what) {
 int depth_bytes(int depth) {
     switch (depth) {
     case CVGS_DEPTH_8U: case CVGS_DEPTH_8S: return 1;
-    case CVGS_DEPTH_16U: case CVGS_DEPTH_16S: case CVGS_DEPTH_16F: return 2;
+    case CVGS_DEPTH_16U: case CVGS_DEPTH_16S: case CVGS_DEPTH_16F: case kDepthBF16: return 2;
     case CVGS_DEPTH_32S: case CVGS_DEPTH_32F: return 4;
     case CVGS_DEPTH_64F: return 8;
     }
     return 0;
+}
+
+// The depth of a public element type as ChainArgs carries it: CV_16BF (depth 16F with CVGS_TYPE_FLAG_BF16) becomes kDepthBF16.
+// The flag means nothing beside another depth (today's handling of the bits above the channel field: ignored).
+int type_depth(int type) {
+    return CVGS_TYPE_DEPTH(type) == CVGS_DEPTH_16F && CVGS_TYPE_IS_BF16(type) ? kDepthBF16 : CVGS_TYPE_DEPTH(type);
+}
+// The destination depth of a CAST / CAST_TRUNC stage (aux): 8U .. 16F or CVGS_DEPTH_16BF; -1 for anything else.
+int cast_depth(int aux) {
+    if (aux == CVGS_DEPTH_16BF) return kDepthBF16;
+    return aux >= CVGS_DEPTH_8U && aux <= CVGS_DEPTH_16F ? aux : -1;
 }
 
 bool is_resize(int kind) { return kind == CVGS_READ_RESIZE_LINEAR || kind == CVGS_READ_NV12_RESIZE_LINEAR; }
@@ -137,15 +159,13 @@ int walk_program(const cvgs_chain_desc* ch, int depth, int cn, int* out_depth, i
         switch (op.opcode) {
         case CVGS_OP_NOP: break;
         case CVGS_OP_CAST:
-            if (op.aux < CVGS_DEPTH_8U || op.aux > CVGS_DEPTH_16F) return fail(CVGS_ERR_INVALID, "CAST: bad destination depth");
-            depth = op.aux;
-            break;
         case CVGS_OP_CAST_TRUNC:
-            if (op.aux < CVGS_DEPTH_8U || op.aux > CVGS_DEPTH_16F) return fail(CVGS_ERR_INVALID, "CAST: bad destination depth");
-            depth = op.aux;
+            if (cast_depth(op.aux) < 0) return fail(CVGS_ERR_INVALID, "CAST: bad destination depth");
+            depth = cast_depth(op.aux);
             break;
         case CVGS_OP_MUL: case CVGS_OP_ADD: case CVGS_OP_SUB: case CVGS_OP_DIV:
             if (depth == CVGS_DEPTH_16F) return fail(CVGS_ERR_UNSUPPORTED, "arithmetic stages on CV_16F values (convertTo CV_32F first)");
+            if (depth == kDepthBF16) return fail(CVGS_ERR_UNSUPPORTED, "arithmetic stages on CV_16BF (bf16) values (convertTo CV_32F first)");
             break;
         case CVGS_OP_REORDER:
             for (int c = 0; c < cn; ++c)
@@ -167,6 +187,7 @@ int walk_program(const cvgs_chain_desc* ch, int depth, int cn, int* out_depth, i
                 if (((op.aux >> (2 * c)) & 3) >= cn) return fail(CVGS_ERR_INVALID, "GRAY: source channel out of range");
             if (depth == CVGS_DEPTH_32S || depth == CVGS_DEPTH_64F || depth == CVGS_DEPTH_16F)
                 return fail(CVGS_ERR_UNSUPPORTED, "GRAY on CV_32S / CV_64F / CV_16F");
+            if (depth == kDepthBF16) return fail(CVGS_ERR_UNSUPPORTED, "GRAY on CV_16BF (bf16) values");
             cn = 1;
             break;
         default: return fail(CVGS_ERR_INVALID, "unknown opcode");
@@ -189,10 +210,10 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
     if (rd.batch < 1 || rd.batch > 65535) return fail(CVGS_ERR_INVALID, "batch must be in [1, 65535]");
     if (rd.used_planes < 0 || rd.used_planes > rd.batch) return fail(CVGS_ERR_INVALID, "used_planes out of range");
     if (!rd.src) return fail(CVGS_ERR_INVALID, "read.src is null");
-    const int sdepth = CVGS_TYPE_DEPTH(rd.src_type), scn = CVGS_TYPE_CN(rd.src_type);
+    const int sdepth = type_depth(rd.src_type), scn = CVGS_TYPE_CN(rd.src_type);
     if (scn > 4) return fail(CVGS_ERR_INVALID, "bad source type");
-    // CV_64F / CV_16F sources: per-pixel reads and the bilinear resize (taps are cast to float, the output is CV_32F, reference
-    // include/cvGPUSpeedup.cuh:227); CV_16F also as a warp source.  A CV_64F warp source has no kernel.
+    // CV_64F / CV_16F / CV_16BF sources: per-pixel reads and the bilinear resize (taps are cast to float, the output is CV_32F, reference
+    // include/cvGPUSpeedup.cuh:227); CV_16F / CV_16BF also as a warp source.  A CV_64F warp source has no kernel.
     if (is_nv12(rd.kind)) {
         if (rd.yuv_layout < CVGS_YUV_NV12 || rd.yuv_layout > CVGS_YUV_P010) return fail(CVGS_ERR_INVALID, "bad yuv_layout");
         if (rd.yuv_range < CVGS_YUV_FULL || rd.yuv_range > CVGS_YUV_LIMITED) return fail(CVGS_ERR_INVALID, "bad yuv_range");
@@ -338,6 +359,7 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
         if (ch->ops[k].opcode == CVGS_OP_NOP) continue;
         Pg.opcode[n] = ch->ops[k].opcode;
         Pg.aux[n] = ch->ops[k].aux;
+        if (ch->ops[k].opcode == CVGS_OP_CAST || ch->ops[k].opcode == CVGS_OP_CAST_TRUNC) Pg.aux[n] = cast_depth(ch->ops[k].aux); // (walk_program below refuses a bad one)
         // 2 bits per output channel: bits beyond the stage's channels mean nothing (walk_program checks the ones that do), but the
         // kernels' program matching compares the whole word -- a binding that fills all four selectors ("3,2,1,0 | 3 << 6" on a
         // 3-channel value) must get the same specialised kernel as the facade's spelling
@@ -367,7 +389,7 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
         for (int k = 0; k < ch->n_ops; ++k) {
             const cvgs_op& op = ch->ops[k];
             if (op.opcode == CVGS_OP_NOP) continue;
-            if (op.opcode == CVGS_OP_CAST || op.opcode == CVGS_OP_CAST_TRUNC) depth = op.aux;
+            if (op.opcode == CVGS_OP_CAST || op.opcode == CVGS_OP_CAST_TRUNC) depth = cast_depth(op.aux);
             const bool arith = op.opcode == CVGS_OP_MUL || op.opcode == CVGS_OP_ADD || op.opcode == CVGS_OP_SUB || op.opcode == CVGS_OP_DIV;
             if (arith && depth <= CVGS_DEPTH_32S) {
                 L.int_arith = true;
@@ -391,7 +413,7 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
 
     // ---- write stage ----
     if (wr.kind < CVGS_WRITE_PIXEL_2D || wr.kind > CVGS_WRITE_PIXEL_2D_BATCH) return fail(CVGS_ERR_INVALID, "bad write kind");
-    if (CVGS_TYPE_DEPTH(wr.dst_type) != L.final_depth || CVGS_TYPE_CN(wr.dst_type) != L.final_cn)
+    if (type_depth(wr.dst_type) != L.final_depth || CVGS_TYPE_CN(wr.dst_type) != L.final_cn)
         return fail(CVGS_ERR_INVALID, "write type does not match the type produced by the last stage");
     WriteArgs& Wa = L.args.write;
     Wa.kind = wr.kind;
@@ -1337,7 +1359,7 @@ int cvgs_plane_table_build(const cvgs_read_desc* read, void* host_out) {
     const int out_cn = is_nv12(read->kind) ? (read->yuv_alpha ? 4 : 3) : CVGS_TYPE_CN(read->src_type);
     const int out_depth = (is_resize(read->kind) || is_nv12(read->kind)) ? CVGS_DEPTH_32F : CVGS_TYPE_DEPTH(read->src_type);
     ch.write.kind = CVGS_WRITE_PIXEL_3D;
-    ch.write.dst_type = CVGS_MAKETYPE(out_depth, out_cn);
+    ch.write.dst_type = CVGS_MAKETYPE(out_depth, out_cn) | (out_depth == CVGS_DEPTH_16F ? (read->src_type & CVGS_TYPE_FLAG_BF16) : 0);
     ch.write.data = (void*)(uintptr_t)16;
     ch.write.planes = read->batch;
     Lowered L;
@@ -1474,7 +1496,8 @@ int cvgs_circular_update(cvgs_circular_t ct, const cvgs_chain_desc* chain, cvgs_
     if (wk == CVGS_WRITE_PIXEL_3D) {
         if (ct->color_planes != 1 || one.write.dst_type != ct->elem_type)
             return fail(CVGS_ERR_INVALID, "packed write needs COLOR_PLANES == 1 and the tensor's element type");
-    } else if (out_cn != ct->color_planes || CVGS_MAKETYPE(CVGS_TYPE_DEPTH(one.write.dst_type), 1) != ct->elem_type) {
+    } else if (out_cn != ct->color_planes ||
+               (CVGS_MAKETYPE(CVGS_TYPE_DEPTH(one.write.dst_type), 1) | (type_depth(one.write.dst_type) == kDepthBF16 ? CVGS_TYPE_FLAG_BF16 : 0)) != ct->elem_type) {
         return fail(CVGS_ERR_INVALID, "split write does not match the tensor's planes / element type");
     }
     if (one.write.n_mirrors) return fail(CVGS_ERR_INVALID, "mirrors cannot be combined with a CircularTensor update");

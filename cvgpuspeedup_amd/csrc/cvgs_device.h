@@ -12,6 +12,15 @@
 
 namespace cvgs {
 
+// CV_16BF values inside ChainArgs (ReadArgs::depth, WriteArgs::depth, the aux of a CAST / CAST_TRUNC stage): the lowering turns the
+// public spelling (depth 16F | CVGS_TYPE_FLAG_BF16) into this depth code of its own, so that no test "depth == CVGS_DEPTH_16F" of a
+// launcher can take a bf16 chain for an fp16 one -- a launcher that was not taught bf16 declines it.  Never seen outside the engine.
+static constexpr int kDepthBF16 = 8;
+
+// The name of a bf16 store kernel: its fp16 twin's name with the "f16" that names the store type spelled "bf16" (interned: the
+// returned pointer lives as long as the library).  Implemented in cvgs_api.cpp.
+const char* bf16_kernel_name(const char* f16_name);
+
 // Per-plane read parameters, precomputed on the host in double precision so that the device never
 // re-derives a scale factor (bit-exactness of fx/fy is part of the parity contract).
 struct PlaneParams {        // 48 bytes
@@ -101,6 +110,14 @@ static_assert(sizeof(KernArgs<CVGS_KERNARG_PLANES>) <= 4096, "kernel-argument bl
 // (~18 us per eager call) and cannot be captured into a HIP graph.
 static constexpr int kKernargPlanesBig = CVGS_KERNARG_PLANES_MAX;
 static_assert(sizeof(KernArgs<kKernargPlanesBig>) <= 16384, "large kernel-argument block: 16 KB");
+
+// Does a chain read, compute or write a CV_16BF value?  The fast launchers that were not taught bf16 (all but K1) decline such chains.
+inline bool chain_has_bf16(const ChainArgs& c) {
+    if (c.read.depth == kDepthBF16 || c.write.depth == kDepthBF16) return true;
+    for (int k = 0; k < c.prog.n && k < CVGS_MAX_OPS; ++k)
+        if ((c.prog.opcode[k] == CVGS_OP_CAST || c.prog.opcode[k] == CVGS_OP_CAST_TRUNC) && c.prog.aux[k] == kDepthBF16) return true;
+    return false;
+}
 
 // Extra write targets (cvgs_write_desc.mirrors): the same values at the same element offsets in up to 7 more tensors
 // (the peers' copies of the sharded [N,C,H,W] tensor).  Travels as its own kernel argument to the kernels that

@@ -101,13 +101,28 @@ static hipError_t launch_push_prog(int prog_id, const KernArgs<1>& a, const PwGe
 // Returns 1 if it took the update (new frame + all copies in ONE launch), 0 if not eligible, <0 on error.
 // `dev` (capturable handles): the kernel derives the count-dependent destinations and the n_jobs copy jobs itself (copy_jobs unused;
 // n_jobs = (BATCH - 1) * planes, or 0 for a mirrored ring); the caller advances the device-side count behind it.
+// bf16 (CV_16BF) elements: the fp16 instantiations' twins with OT = __bf16, compiled in k_circular_bf16.hip (this file with
+// CVGS_CIRC_BF16_TU)
+hipError_t circ_push_launch_bf16(int cn, int prog_id, const KernArgs<1>& a, const PwGeom& g, const CopyArgs& jobs, const PushGeom& pg, const CircDev* dev,
+                                 hipStream_t s);
+#ifdef CVGS_CIRC_BF16_TU
+hipError_t circ_push_launch_bf16(int cn, int prog_id, const KernArgs<1>& a, const PwGeom& g, const CopyArgs& jobs, const PushGeom& pg, const CircDev* dev,
+                                 hipStream_t s) {
+    switch (cn) {
+    case 1: return launch_push_prog<1, __bf16>(prog_id, a, g, jobs, pg, dev, s);
+    case 2: return launch_push_prog<2, __bf16>(prog_id, a, g, jobs, pg, dev, s);
+    case 3: return launch_push_prog<3, __bf16>(prog_id, a, g, jobs, pg, dev, s);
+    default: return launch_push_prog<4, __bf16>(prog_id, a, g, jobs, pg, dev, s);
+    }
+}
+#else
 int launch_circular_push(const ChainArgs& c_in, const PlaneParams& plane, const CopyJob* copy_jobs, int n_jobs, size_t plane_bytes,
                          uint32_t chain_flags, void* stream, const CircDev* dev) {
     ChainArgs c;
     PwGeom g;
     int prog_id = 0;
-    bool f16 = false;
-    if (!pointwise4_plan(c_in, 1, chain_flags, c, g, prog_id, f16)) return 0;
+    bool f16 = false, bf16 = false;
+    if (!pointwise4_plan(c_in, 1, chain_flags, c, g, prog_id, f16, nullptr, &bf16)) return 0;
     if (prog_id == 3) return 0; // non-u8 sources: chain kernel + copy kernel
     if (n_jobs < (dev ? 0 : 1) || n_jobs > kMaxCopyJobs || plane_bytes % 16) return 0;
     if (dev) {
@@ -132,7 +147,9 @@ int launch_circular_push(const ChainArgs& c_in, const PlaneParams& plane, const 
     if (pg.blocks_per_job < 1) pg.blocks_per_job = 1;
     hipStream_t s = (hipStream_t)stream;
     hipError_t e;
-    if (f16) {
+    if (bf16) {
+        e = circ_push_launch_bf16(c.read.cn, prog_id, a, g, jobs, pg, dev, s);
+    } else if (f16) {
         switch (c.read.cn) {
         case 1: e = launch_push_prog<1, _Float16>(prog_id, a, g, jobs, pg, dev, s); break;
         case 2: e = launch_push_prog<2, _Float16>(prog_id, a, g, jobs, pg, dev, s); break;
@@ -281,5 +298,6 @@ int launch_plane_copies(const CopyJob* jobs, int n_jobs, size_t bytes, void* str
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+#endif // CVGS_CIRC_BF16_TU
 
 } // namespace cvgs

@@ -74,16 +74,31 @@ __device__ __forceinline__ void depth_range(int depth, float& lo, float& hi) {
 // fp32 -> binary16 -> fp32: round to nearest even, overflow to +-inf (v_cvt_f16_f32); a CV_16F value lives in the
 // work pixel as the float it converts to exactly
 __device__ __forceinline__ float round_half(float v) { return (float)(_Float16)v; }
+// fp32 -> bfloat16 -> fp32: round to nearest even, overflow to +-inf (v_cvt_pk_bf16_f32); a CV_16BF value lives in the work pixel
+// the same way (kDepthBF16)
+__device__ __forceinline__ float round_bf16(float v) { return (float)(__bf16)v; }
+// the float a default value (already in the float type of the read's output) becomes when that type is a 16-bit float
+__device__ __forceinline__ float round_to_depth(float v, int depth) {
+    return depth == CVGS_DEPTH_16F ? round_half(v) : (depth == kDepthBF16 ? round_bf16(v) : v);
+}
 
-template <bool TRUNC = false>
+// BF: the kernel may meet CV_16BF values (the interpreted kernels only: a fast kernel's host-side plan keeps every cast to or from
+// bf16 out of the program it runs, so their code does not carry the branch)
+template <bool TRUNC = false, bool BF = false>
 __device__ __forceinline__ void cast_px(Px& p, int cn, int src_depth, int dst_depth) {
     if (src_depth == dst_depth) return;
-    if (src_depth == CVGS_DEPTH_16F) src_depth = CVGS_DEPTH_32F; // already an exact float
+    if (src_depth == CVGS_DEPTH_16F || (BF && src_depth == kDepthBF16)) src_depth = CVGS_DEPTH_32F; // already an exact float
     if (src_depth == dst_depth) return;
     if (dst_depth == CVGS_DEPTH_16F) {
 #pragma unroll
         for (int c = 0; c < 4; ++c)
             if (c < cn) p.v[c] = round_half(src_depth == CVGS_DEPTH_32S ? (float)as_int(p.v[c]) : p.v[c]);
+        return;
+    }
+    if (BF && dst_depth == kDepthBF16) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (c < cn) p.v[c] = round_bf16(src_depth == CVGS_DEPTH_32S ? (float)as_int(p.v[c]) : p.v[c]);
         return;
     }
     if (dst_depth == CVGS_DEPTH_32F) {
@@ -179,11 +194,11 @@ __device__ __forceinline__ void apply_op(int opc, int aux, const float* operand,
     }
     switch (opc) {
     case CVGS_OP_CAST:
-        cast_px(p, cn, depth, aux);
+        cast_px<false, INTA>(p, cn, depth, aux);
         depth = aux;
         break;
     case CVGS_OP_CAST_TRUNC:
-        cast_px<true>(p, cn, depth, aux);
+        cast_px<true, INTA>(p, cn, depth, aux);
         depth = aux;
         break;
     case CVGS_OP_MUL:
@@ -507,6 +522,10 @@ __device__ __forceinline__ void load_px(const uint8_t* row, int depth, int cn, i
 #pragma unroll
         for (int c = 0; c < 4; ++c) if (c < cn) p.v[c] = (float)((const _Float16*)row)[x * cn + c];
         break;
+    case kDepthBF16:
+#pragma unroll
+        for (int c = 0; c < 4; ++c) if (c < cn) p.v[c] = (float)((const __bf16*)row)[x * cn + c];
+        break;
     default: // 32S raw bits, 32F
 #pragma unroll
         for (int c = 0; c < 4; ++c) if (c < cn) p.v[c] = ((const float*)row)[x * cn + c];
@@ -601,6 +620,8 @@ __device__ __forceinline__ void nv12_px(const PlaneParams& P, int x, int y, cons
 }
 
 // ---- write stages ------------------------------------------------------------------------------
+// BF: the kernel may write CV_16BF values (the interpreted kernels only, like cast_px's BF)
+template <bool BF = false>
 __device__ __forceinline__ void store_elem(uint8_t* base, size_t idx, int depth, float v) {
     switch (depth) {
     case CVGS_DEPTH_8U: base[idx] = (uint8_t)v; break;
@@ -608,10 +629,17 @@ __device__ __forceinline__ void store_elem(uint8_t* base, size_t idx, int depth,
     case CVGS_DEPTH_16U: ((uint16_t*)base)[idx] = (uint16_t)v; break;
     case CVGS_DEPTH_16S: ((int16_t*)base)[idx] = (int16_t)v; break;
     case CVGS_DEPTH_16F: ((_Float16*)base)[idx] = (_Float16)v; break;
+    case kDepthBF16:
+        if constexpr (BF) {
+            ((__bf16*)base)[idx] = (__bf16)v;
+            break;
+        }
+        [[fallthrough]];
     default: ((float*)base)[idx] = v; break; // 32S raw bits, 32F
     }
 }
 
+template <bool BF = false>
 __device__ __forceinline__ void write_px(const WriteArgs& w, const DstPlane* dst_planes, int x, int y, int z,
                                          const Px& p, int depth, int cn) {
     const size_t W = (size_t)w.width;
@@ -619,24 +647,24 @@ __device__ __forceinline__ void write_px(const WriteArgs& w, const DstPlane* dst
     case CVGS_WRITE_PIXEL_2D: {
         uint8_t* row = w.data + (size_t)y * (size_t)w.step;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) if (c < cn) store_elem(row, (size_t)x * cn + c, depth, p.v[c]);
+        for (int c = 0; c < 4; ++c) if (c < cn) store_elem<BF>(row, (size_t)x * cn + c, depth, p.v[c]);
         break;
     }
     case CVGS_WRITE_PIXEL_2D_BATCH: {
         const DstPlane d = dst_planes[z];
         uint8_t* row = d.data + (size_t)y * (size_t)d.step;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) if (c < cn) store_elem(row, (size_t)x * cn + c, depth, p.v[c]);
+        for (int c = 0; c < 4; ++c) if (c < cn) store_elem<BF>(row, (size_t)x * cn + c, depth, p.v[c]);
         break;
     }
     case CVGS_WRITE_PIXEL_3D: {
         const size_t pix = (size_t)z * w.img_stride + (size_t)y * W + x;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) if (c < cn) store_elem(w.data, pix * cn + c, depth, p.v[c]);
+        for (int c = 0; c < 4; ++c) if (c < cn) store_elem<BF>(w.data, pix * cn + c, depth, p.v[c]);
         if (w.data2) {
             const size_t pix2 = (size_t)z * w.img_stride2 + (size_t)y * W + x;
 #pragma unroll
-            for (int c = 0; c < 4; ++c) if (c < cn) store_elem(w.data2, pix2 * cn + c, depth, p.v[c]);
+            for (int c = 0; c < 4; ++c) if (c < cn) store_elem<BF>(w.data2, pix2 * cn + c, depth, p.v[c]);
         }
         break;
     }
@@ -644,12 +672,12 @@ __device__ __forceinline__ void write_px(const WriteArgs& w, const DstPlane* dst
     case CVGS_WRITE_TENSOR_T_SPLIT:
 #pragma unroll
         for (int c = 0; c < 4; ++c)
-            if (c < cn) store_elem(w.data, (size_t)z * w.img_stride + (size_t)c * w.ch_stride + (size_t)y * W + x, depth, p.v[c]);
+            if (c < cn) store_elem<BF>(w.data, (size_t)z * w.img_stride + (size_t)c * w.ch_stride + (size_t)y * W + x, depth, p.v[c]);
         if (w.data2) {
 #pragma unroll
             for (int c = 0; c < 4; ++c)
                 if (c < cn)
-                    store_elem(w.data2, (size_t)z * w.img_stride2 + (size_t)c * w.ch_stride2 + (size_t)y * W + x, depth, p.v[c]);
+                    store_elem<BF>(w.data2, (size_t)z * w.img_stride2 + (size_t)c * w.ch_stride2 + (size_t)y * W + x, depth, p.v[c]);
         }
         break;
     case CVGS_WRITE_SPLIT_2D:
@@ -657,7 +685,7 @@ __device__ __forceinline__ void write_px(const WriteArgs& w, const DstPlane* dst
         for (int c = 0; c < 4; ++c) {
             if (c < cn) {
                 const DstPlane d = dst_planes[(size_t)z * cn + c];
-                store_elem(d.data + (size_t)y * (size_t)d.step, (size_t)x, depth, p.v[c]);
+                store_elem<BF>(d.data + (size_t)y * (size_t)d.step, (size_t)x, depth, p.v[c]);
             }
         }
         break;

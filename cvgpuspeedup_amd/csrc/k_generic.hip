@@ -37,7 +37,7 @@ __global__ __launch_bounds__(256) void k_generic(const KernArgs<NPL> a, const Mi
         // fk::BatchRead<N,CONDITIONAL_WITH_DEFAULT>: default value, then the whole chain
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-            p.v[k] = depth == CVGS_DEPTH_32S ? from_int((int)r.bg[k]) : (depth == CVGS_DEPTH_16F ? round_half(r.bg[k]) : r.bg[k]);
+            p.v[k] = depth == CVGS_DEPTH_32S ? from_int((int)r.bg[k]) : round_to_depth(r.bg[k], depth);
     } else {
         PlaneParams P;
         if constexpr (NPL == 0) P = r.table[z];
@@ -79,13 +79,13 @@ __global__ __launch_bounds__(256) void k_generic(const KernArgs<NPL> a, const Mi
     InterpProgInt::run(c.prog, p, depth, cn);
 
     const DstPlane* dst = c.write.table ? c.write.table : c.dst_inline;
-    write_px(c.write, dst, x, y, z, p, depth, cn);
+    write_px<true>(c.write, dst, x, y, z, p, depth, cn);
     // cvgs_write_desc.mirrors (tensor kinds): the same value at the same offsets of every further tensor
     for (int m = 0; m < mirrors.n; ++m) {
         WriteArgs w = c.write;
         w.data = mirrors.p[m];
         w.data2 = nullptr;
-        write_px(w, dst, x, y, z, p, depth, cn);
+        write_px<true>(w, dst, x, y, z, p, depth, cn);
     }
 }
 

@@ -35,12 +35,12 @@ __device__ __forceinline__ void int_range64(int depth, double& lo, double& hi) {
 
 template <bool TRUNC = false>
 __device__ __forceinline__ void cast64(Px64& p, int cn, int src, int dst) {
-    if (src == CVGS_DEPTH_16F) src = CVGS_DEPTH_32F; // a half value is carried as the float (double) it equals
+    if (src == CVGS_DEPTH_16F || src == kDepthBF16) src = CVGS_DEPTH_32F; // a half / bf16 value is carried as the float (double) it equals
     if (src == dst || dst == CVGS_DEPTH_64F) return; // widening to double is exact
-    if (dst == CVGS_DEPTH_16F) { // through float, then round to nearest even once more (the oracle's order: (float)d, then half)
+    if (dst == CVGS_DEPTH_16F || dst == kDepthBF16) { // through float, then round to nearest even once more (the oracle's order: (float)d, then half)
 #pragma unroll
         for (int c = 0; c < 4; ++c)
-            if (c < cn) p.v[c] = (double)round_half((float)p.v[c]);
+            if (c < cn) p.v[c] = (double)round_to_depth((float)p.v[c], dst);
         return;
     }
     if (dst == CVGS_DEPTH_32F) {
@@ -127,6 +127,7 @@ __device__ __forceinline__ void load64(const uint8_t* row, int depth, int cn, in
             case CVGS_DEPTH_32S: p.v[c] = (double)((const int32_t*)row)[e]; break;
             case CVGS_DEPTH_32F: p.v[c] = (double)((const float*)row)[e]; break;
             case CVGS_DEPTH_16F: p.v[c] = (double)(float)((const _Float16*)row)[e]; break;
+            case kDepthBF16: p.v[c] = (double)(float)((const __bf16*)row)[e]; break;
             default: p.v[c] = ((const double*)row)[e]; break;
             }
         }
@@ -142,6 +143,7 @@ __device__ __forceinline__ void store64(uint8_t* base, size_t idx, int depth, do
     case CVGS_DEPTH_32S: ((int32_t*)base)[idx] = (int32_t)v; break;
     case CVGS_DEPTH_32F: ((float*)base)[idx] = (float)v; break;
     case CVGS_DEPTH_16F: ((_Float16*)base)[idx] = (_Float16)(float)v; break;
+    case kDepthBF16: ((__bf16*)base)[idx] = (__bf16)(float)v; break;
     default: ((double*)base)[idx] = v; break;
     }
 }
@@ -214,7 +216,7 @@ __global__ __launch_bounds__(256) void k_generic64(const KernArgs64<NPL> a) {
     if (z >= r.used) {
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-            p.v[k] = depth == CVGS_DEPTH_32S ? (double)(int)r.bg[k] : (depth == CVGS_DEPTH_16F ? (double)round_half(r.bg[k]) : (double)r.bg[k]);
+            p.v[k] = depth == CVGS_DEPTH_32S ? (double)(int)r.bg[k] : (double)round_to_depth(r.bg[k], depth);
     } else {
         PlaneParams P;
         if constexpr (NPL == 0) P = r.table[z];

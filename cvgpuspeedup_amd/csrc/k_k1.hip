@@ -23,13 +23,16 @@
 //    by this kernel, so it should not wait in L2 for the end-of-kernel write-back.
 //  * small launches use 1 row per wave (maximum parallelism, shortest critical path), large ones 4 (amortises the
 //    column geometry).
-#include "k_k1_impl.hpp"
+#include "k_k1_bf16.hpp"
 
 namespace cvgs {
 
 // the planar-tensor variants of 3- / 4-channel sources live in k_k1_c3.hip / k_k1_c4.hip (parallel compilation)
 hipError_t k1_launch_planar_c3(int src, bool f16, int prog_id, bool table, int rpw, const ChainArgs& c, const PlaneParams* ip, int ni, int out_cn, LaunchCtx& s);
 hipError_t k1_launch_planar_c4(int src, bool f16, int prog_id, bool table, int rpw, const ChainArgs& c, const PlaneParams* ip, int ni, int out_cn, LaunchCtx& s);
+// ... and the bf16 (CV_16BF) store variants of every fp16 one, in k_k1_bf16_c3.hip / k_k1_bf16_c4.hip (mode: k_k1_bf16.hpp K1Bf16Mode)
+hipError_t k1_launch_bf16_c3(int mode, int prog_id, bool canon, bool table, int rpw, const ChainArgs& c, const PlaneParams* ip, int ni, int out_cn, LaunchCtx& s);
+hipError_t k1_launch_bf16_c4(int mode, int prog_id, bool canon, bool table, int rpw, const ChainArgs& c, const PlaneParams* ip, int ni, int out_cn, LaunchCtx& s);
 
 int launch_k1(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_inline, LaunchCtx& ctx, bool dry_run, LaunchInfo* info, uint32_t chain_flags) {
     const MirrorArgs& mirrors = ctx.mirrors;
@@ -37,12 +40,12 @@ int launch_k1(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_inl
     const int n_segs = ctx.n_segs;
     void* const stream = ctx.stream;
     const ReadArgs& r = c_in.read;
-    // eligibility: 8U / 16U / 16S C3/C4 resize read, fp32 planar tensor write -- or, for 8U sources, an fp16 planar
-    // tensor whose conversion is the chain's LAST stage (the half-precision hand-off option)
+    // eligibility: 8U / 16U / 16S C3/C4 resize read, fp32 planar tensor write -- or, for 8U sources, an fp16 / bf16 planar
+    // tensor whose conversion is the chain's LAST stage (the 16-bit float hand-off options)
     if (r.kind != CVGS_READ_RESIZE_LINEAR || r.cn < 1 || r.cn > 4) return 0;
     if (r.depth != CVGS_DEPTH_8U && r.depth != CVGS_DEPTH_16U && r.depth != CVGS_DEPTH_16S && r.depth != CVGS_DEPTH_32F) return 0;
     const bool few = r.cn < 3; // 1 / 2 channels: planar fp32, or packed fp32 / u8
-    if (few && (c_in.write.kind == CVGS_WRITE_SPLIT_2D || c_in.write.depth == CVGS_DEPTH_16F)) return 0;
+    if (few && (c_in.write.kind == CVGS_WRITE_SPLIT_2D || c_in.write.depth == CVGS_DEPTH_16F || c_in.write.depth == kDepthBF16)) return 0;
     const int wk = c_in.write.kind;
     const bool planar = wk == CVGS_WRITE_TENSOR_SPLIT || wk == CVGS_WRITE_TENSOR_T_SPLIT;
     const bool packed = wk == CVGS_WRITE_PIXEL_2D || wk == CVGS_WRITE_PIXEL_3D;
@@ -52,7 +55,7 @@ int launch_k1(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_inl
     if ((mirrors.n > 0 || segs) && (!planar || c_in.write.data2)) return 0; // extra targets / fused chains: planar tensors only
     // mirrors: u8 C3/C4 -> fp32 planar with the planes in the kernel arguments (cfg #5: 64 crops per GPU); the rest is
     // the interpreted kernel's business
-    if (mirrors.n > 0 && (r.depth != CVGS_DEPTH_8U || r.cn < 3 || r.table || segs || (c_in.write.depth != CVGS_DEPTH_32F && c_in.write.depth != CVGS_DEPTH_16F)))
+    if (mirrors.n > 0 && (r.depth != CVGS_DEPTH_8U || r.cn < 3 || r.table || segs || (c_in.write.depth != CVGS_DEPTH_32F && c_in.write.depth != CVGS_DEPTH_16F && c_in.write.depth != kDepthBF16)))
         return 0;
     if (segs && (n_segs < 1 || n_segs > CVGS_MAX_CHAINS)) return 0;
     // fused chains without a table: segments AND planes in the kernel arguments (KernArgsManyInline; u8 sources, 3 / 4 channels)
@@ -60,7 +63,9 @@ int launch_k1(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_inl
     if (inline_many && (!inline_planes || n_inline < 1 || n_inline > kManyInlineLarge || r.depth != CVGS_DEPTH_8U || few)) return 0;
     // more than CVGS_KERNARG_PLANES descriptors in the kernel arguments: the 3- / 4-channel planar-tensor kernels only
     if (!r.table && !inline_many && n_inline > CVGS_KERNARG_PLANES && (n_inline > kKernargPlanesBig || !planar || few)) return 0;
-    const bool f16 = c_in.write.depth == CVGS_DEPTH_16F;
+    // bf16 targets take the fp16 ones' path, with their kernels' bf16 twins (every "f16" below means "a 16-bit float store" from here on)
+    const bool bf16 = c_in.write.depth == kDepthBF16;
+    const bool f16 = c_in.write.depth == CVGS_DEPTH_16F || bf16;
     const bool u8out = c_in.write.depth == CVGS_DEPTH_8U;
     const bool i16out = c_in.write.depth == CVGS_DEPTH_16U || c_in.write.depth == CVGS_DEPTH_16S;
     if (!f16 && !u8out && !i16out && c_in.write.depth != CVGS_DEPTH_32F) return 0;
@@ -188,12 +193,18 @@ int launch_k1(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_inl
                                                     {"k1_u8c4_packed_f32_arith", "k1_u8c4_packed_f16_arith", "k1_u8c4_packed_u8_arith"}};
             info->kernel = names_canon[r.cn == 4][u8out ? 2 : (f16 ? 1 : 0)];
         } else info->kernel = names_other[r.cn == 4][split2d ? 3 : (u8out ? 2 : (f16 ? 1 : 0))];
+        if (bf16) info->kernel = bf16_kernel_name(info->kernel);
     }
     if (dry_run) return 1;
     LaunchCtx& s = ctx;
     const int out_cn = c.write.cn;
     hipError_t e;
-    if (mirrors.n > 0) {
+    if (bf16) {
+        const int mode = mirrors.n > 0 ? K1_BF16_MIRRORED : (planar ? K1_BF16_PLANAR : K1_BF16_PACKED);
+        const int pid = mirrors.n > 0 ? prog_id : planar_prog;
+        e = r.cn == 3 ? k1_launch_bf16_c3(mode, pid, canon_packed, table, rpw, c, inline_planes, n_inline, out_cn, s)
+                      : k1_launch_bf16_c4(mode, pid, canon_packed, table, rpw, c, inline_planes, n_inline, out_cn, s);
+    } else if (mirrors.n > 0) {
         // one row per wave (a 64-crop launch is in the latency regime), planes in the kernel arguments
         // fp16 tensors (the half-precision hand-off) halve the bytes every xGMI link has to carry
         auto mir_t = [&](auto prog_tag, auto ot_tag) {

@@ -518,6 +518,15 @@ static hipError_t launch_n12(const ChainArgs& c, const PlaneParams* ip, int ni, 
     return launch_n12_cn<Prog, OT, false, false, false>(c, ip, ni, g, s);
 }
 
+// bf16 (CV_16BF) planar tensors: the fp16 instantiations' twins with OT = __bf16, compiled in k_nv12_bf16.hip (this file included with
+// CVGS_K4_BF16_TU, so the bf16 kernels build in parallel with the others).  prog: 0 swap-mul-sub-div, 1 canonical, 2 interpreted.
+hipError_t k4_launch_bf16(int prog, const ChainArgs& c, const PlaneParams* ip, int ni, const N12Geom& g, const N12Many& s, bool win);
+#ifdef CVGS_K4_BF16_TU
+hipError_t k4_launch_bf16(int prog, const ChainArgs& c, const PlaneParams* ip, int ni, const N12Geom& g, const N12Many& s, bool win) {
+    return prog == 0 ? launch_n12<N12SwapMulSubDiv, __bf16>(c, ip, ni, g, s, win)
+                     : (prog == 1 ? launch_n12<K1CanonProg, __bf16>(c, ip, ni, g, s, win) : launch_n12<InterpProg, __bf16>(c, ip, ni, g, s, win));
+}
+#else
 // Returns 1 if it took the chain, 0 if not eligible, <0 on error.
 // Can K4 serve these planes?  Rows wide enough for the 4-byte chroma window; stretch geometry for the callers that cannot pick
 // the windowed instantiation (fused chains, staged tables).
@@ -542,10 +551,13 @@ int launch_nv12(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_i
     const int n_segs = ctx.n_segs;
     void* const stream = ctx.stream;
     const ReadArgs& r = c_in.read;
-    // fp16 planar tensors: the trailing CAST(CV_16F) moves into the store
+    // fp16 / bf16 planar tensors: the trailing CAST(CV_16F / CV_16BF) moves into the store (a bf16 chain of any other shape: the
+    // interpreted kernel); "f16" below means "a 16-bit float store" from here on
     const bool planar_kind = c_in.write.kind == CVGS_WRITE_TENSOR_SPLIT || c_in.write.kind == CVGS_WRITE_TENSOR_T_SPLIT;
-    const bool f16 = planar_kind && c_in.write.depth == CVGS_DEPTH_16F && c_in.prog.n >= 1 &&
-                     c_in.prog.opcode[c_in.prog.n - 1] == CVGS_OP_CAST;
+    const bool trailing_cast = c_in.prog.n >= 1 && c_in.prog.opcode[c_in.prog.n - 1] == CVGS_OP_CAST;
+    const bool bf16 = planar_kind && c_in.write.depth == kDepthBF16 && trailing_cast;
+    if (chain_has_bf16(c_in) && !bf16) return 0;
+    const bool f16 = planar_kind && (c_in.write.depth == CVGS_DEPTH_16F || bf16) && trailing_cast;
     ChainArgs c_cut;
     if (f16) {
         c_cut = c_in;
@@ -667,13 +679,15 @@ int launch_nv12(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_i
     if (info)
         info->kernel = f16 ? (fast_prog ? "k4_nv12_resize_swap_mul_sub_div_f16" : (canon_prog ? "k4_nv12_resize_arith_f16" : "k4_nv12_resize_interp_f16"))
                            : (fast_prog ? "k4_nv12_resize_swap_mul_sub_div" : (fast_rgb ? "k4_nv12_resize_mul_sub_div" : (canon_prog ? "k4_nv12_resize_arith" : "k4_nv12_resize_interp")));
+    if (info && bf16) info->kernel = bf16_kernel_name(info->kernel);
     if (dry_run) return 1;
     const N12Many s{&ctx, segs, n_segs, segs && !r.table ? inline_planes : nullptr, segs && !r.table ? n_inline : 0};
     // the windowed instantiations: an aspect-ratio window or default-value planes (never for fused chains / staged tables, whose
     // callers admit stretch geometry only)
     const bool win = !segs && (r.used != r.batch || !k4_planes_eligible(inline_planes, n_inline, r.dst_w, r.dst_h));
     hipError_t e;
-    if (f16) e = fast_prog ? launch_n12<N12SwapMulSubDiv, _Float16>(c_fd, inline_planes, n_inline, g, s, win)
+    if (bf16) e = k4_launch_bf16(fast_prog ? 0 : (canon_prog ? 1 : 2), c_fd, inline_planes, n_inline, g, s, win);
+    else if (f16) e = fast_prog ? launch_n12<N12SwapMulSubDiv, _Float16>(c_fd, inline_planes, n_inline, g, s, win)
                            : (canon_prog ? launch_n12<K1CanonProg, _Float16>(c_fd, inline_planes, n_inline, g, s, win)
                                          : launch_n12<InterpProg, _Float16>(c_fd, inline_planes, n_inline, g, s, win));
     else if (fast_prog) e = launch_n12<N12SwapMulSubDiv>(c_fd, inline_planes, n_inline, g, s, win);
@@ -681,5 +695,6 @@ int launch_nv12(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_i
     else e = canon_prog ? launch_n12<K1CanonProg>(c_fd, inline_planes, n_inline, g, s, win) : launch_n12<InterpProg>(c_fd, inline_planes, n_inline, g, s, win);
     return e == hipSuccess ? 1 : -(int)e - 1000;
 }
+#endif // CVGS_K4_BF16_TU
 
 } // namespace cvgs

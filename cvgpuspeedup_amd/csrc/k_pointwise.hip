@@ -236,6 +236,21 @@ static hipError_t launch_u8u8_ocn(int ocn, const ChainArgs& c, const PlaneParams
 }
 
 // Returns 1 if it took the chain, 0 if not eligible, <0 on error.
+// bf16 (CV_16BF) targets: the fp16 instantiations' twins with OT = __bf16, compiled in k_pointwise_bf16.hip (this file with
+// CVGS_PW_BF16_TU).  sd: the 4:2:0 layout of a read without resize (SD_NV12 / SD_P010 / SD_I420), -1 for u8 planes.
+hipError_t pw_launch_bf16(int prog_id, int sd, const ChainArgs& c, const PlaneParams* ip, int ni, const PwGeom& g, hipStream_t s);
+#ifdef CVGS_PW_BF16_TU
+hipError_t pw_launch_bf16(int prog_id, int sd, const ChainArgs& c, const PlaneParams* ip, int ni, const PwGeom& g, hipStream_t s) {
+    if (sd < 0) return launch_pw_cn<__bf16>(prog_id, c, ip, ni, g, s);
+    auto go = [&](auto sd_tag) {
+        constexpr int SD = decltype(sd_tag)::value;
+        return g.cn == 3 ? launch_pw<3, ArithProg<3, CVGS_DEPTH_32F>, __bf16, SD>(c, ip, ni, g, s)
+                         : launch_pw<4, ArithProg<4, CVGS_DEPTH_32F>, __bf16, SD>(c, ip, ni, g, s);
+    };
+    return sd == SD_P010 ? go(std::integral_constant<int, SD_P010>{})
+                         : (sd == SD_I420 ? go(std::integral_constant<int, SD_I420>{}) : go(std::integral_constant<int, SD_NV12>{}));
+}
+#else
 static int launch_pointwise_u8u8(const ChainArgs& c, const PlaneParams* ip, int ni, uint32_t chain_flags, hipStream_t s, bool dry_run,
                                  LaunchInfo* info) {
     const ReadArgs& r = c.read;
@@ -309,10 +324,16 @@ static int launch_pointwise_f32f32(const ChainArgs& c, const PlaneParams* ip, in
 
 // Eligibility + geometry of the thread-fused path, shared with the single-launch CircularTensor push (k_circular.hip).
 // On success `c` is the chain to run (an fp16 target's trailing CAST is folded into the store), `g` the geometry.
-bool pointwise4_plan(const ChainArgs& c_in, int n_inline, uint32_t chain_flags, ChainArgs& c, PwGeom& g, int& prog_id, bool& f16, bool* u8out) {
+bool pointwise4_plan(const ChainArgs& c_in, int n_inline, uint32_t chain_flags, ChainArgs& c, PwGeom& g, int& prog_id, bool& f16, bool* u8out,
+                     bool* bf16out) {
     const ReadArgs& r = c_in.read;
     const WriteArgs& w = c_in.write;
     if (chain_flags & CVGS_CHAIN_NO_THREAD_FUSION) return false;
+    // bf16 targets (callers that pass bf16out): the fp16 path; every other bf16 chain (bf16 sources, casts inside the program) is the
+    // interpreted kernel's -- the checks below refuse a program with any cast but the leading CAST(CV_32F) and the trailing one
+    const bool bfw = w.depth == kDepthBF16;
+    if (bf16out) *bf16out = bfw;
+    if (chain_has_bf16(c_in) && !(bfw && bf16out)) return false;
     // 4:2:0 surfaces with interleaved chroma read WITHOUT a resize (the decode-side cvtColor: cvGS::cvtColorNV12 -> ... -> tensor):
     // the value arrives as CV_32F R, G, B[, A], so the chain is a CV_32F chain with out_cn channels
     const bool yuv = r.kind == CVGS_READ_NV12; // every layout: NV12 / NV21 / P010 (interleaved chroma), I420 / YV12 (planar chroma)
@@ -322,7 +343,7 @@ bool pointwise4_plan(const ChainArgs& c_in, int n_inline, uint32_t chain_flags, 
     if (!u8src && sdepth != CVGS_DEPTH_8S && sdepth != CVGS_DEPTH_16U && sdepth != CVGS_DEPTH_16S && sdepth != CVGS_DEPTH_32S &&
         sdepth != CVGS_DEPTH_32F)
         return false;
-    f16 = w.depth == CVGS_DEPTH_16F;
+    f16 = w.depth == CVGS_DEPTH_16F || bfw;
     // packed u8 pixels behind a 4:2:0 read (NV12 -> BGR image): the chain ends with CAST(CV_8U), which the store performs
     const bool u8o = yuv && u8out && w.depth == CVGS_DEPTH_8U && (w.kind == CVGS_WRITE_PIXEL_2D || w.kind == CVGS_WRITE_PIXEL_3D) &&
                      c_in.prog.n >= 1 && c_in.prog.opcode[c_in.prog.n - 1] == CVGS_OP_CAST && c_in.prog.aux[c_in.prog.n - 1] == CVGS_DEPTH_8U;
@@ -331,7 +352,7 @@ bool pointwise4_plan(const ChainArgs& c_in, int n_inline, uint32_t chain_flags, 
     if (f16 && !u8src && !yuv) return false;
     c = c_in;
     if (u8o) c.prog.n -= 1;
-    if (f16) { // fp16 targets: the chain ends with CAST(CV_16F); that conversion happens in the store
+    if (f16) { // fp16 / bf16 targets: the chain ends with CAST(CV_16F / CV_16BF); that conversion happens in the store
         if (c_in.prog.n < (yuv ? 1 : 2) || c_in.prog.opcode[c_in.prog.n - 1] != CVGS_OP_CAST) return false;
         c.prog.n -= 1;
     }
@@ -393,6 +414,7 @@ int launch_pointwise_many(const ChainArgs& c_in, const PlaneParams* planes, int 
     const ReadArgs& r = c_in.read;
     const WriteArgs& w = c_in.write;
     // the hot pointwise shape only: u8 planes read per pixel, an fp32 program, a dense fp32 target (planar tensor or packed pixels)
+    if (chain_has_bf16(c_in)) return 0;
     if (r.kind != CVGS_READ_PIXEL || r.depth != CVGS_DEPTH_8U || r.table || w.data2 || w.depth != CVGS_DEPTH_32F) return 0;
     if (w.kind != CVGS_WRITE_TENSOR_SPLIT && w.kind != CVGS_WRITE_TENSOR_T_SPLIT && w.kind != CVGS_WRITE_PIXEL_3D) return 0;
     if (n_segs < 2 || n_segs > CVGS_MAX_CHAINS || max_batch < 1 || (int64_t)n_segs * max_batch > 65535 || n_planes < 1 || n_planes > kManyInlineLarge) return 0;
@@ -444,8 +466,9 @@ int launch_pointwise(const ChainArgs& c_in, const PlaneParams* inline_planes, in
     PwGeom g;
     int prog_id = 0;
     bool f16 = false;
-    bool u8o = false;
-    if (!pointwise4_plan(c_in, n_inline, chain_flags, c, g, prog_id, f16, &u8o)) return 0;
+    bool u8o = false, bf16 = false;
+    if (chain_has_bf16(c_in) && c_in.write.depth != kDepthBF16) return 0; // (the u8 / u16 / f32 paths above never take a bf16 chain)
+    if (!pointwise4_plan(c_in, n_inline, chain_flags, c, g, prog_id, f16, &u8o, &bf16)) return 0;
     g.narrow = g.w <= 64 ? 2 : (g.w <= 128 ? 1 : 0); // batches of small crops (the reference's 60x120 crops): several rows per wave
     const bool yuv = c.read.kind == CVGS_READ_NV12;
     if (yuv) { // the thread's 4 pixels share 2 chroma pairs: even widths (validated for every 4:2:0 plane) and x0 % 4 == 0
@@ -456,8 +479,13 @@ int launch_pointwise(const ChainArgs& c_in, const PlaneParams* inline_planes, in
                                               {"pointwise4_p010", "pointwise4_p010_u8", "pointwise4_p010_f16"},
                                               {"pointwise4_i420", "pointwise4_i420_u8", "pointwise4_i420_f16"}};
             info->kernel = names[ten ? 1 : (planar_chroma ? 2 : 0)][u8o ? 1 : (f16 ? 2 : 0)];
+            if (bf16) info->kernel = bf16_kernel_name(info->kernel);
         }
         if (dry_run) return 1;
+        if (bf16) {
+            const hipError_t e = pw_launch_bf16(prog_id, ten ? SD_P010 : (planar_chroma ? SD_I420 : SD_NV12), c, inline_planes, n_inline, g, (hipStream_t)stream);
+            return e == hipSuccess ? 1 : -(int)e - 1000;
+        }
         const ProgArgs& p = c.prog;
         const bool norm = p.n == 3 && p.opcode[0] == CVGS_OP_MUL && p.opcode[1] == CVGS_OP_SUB && p.opcode[2] == CVGS_OP_DIV;
         hipStream_t s = (hipStream_t)stream;
@@ -480,6 +508,7 @@ int launch_pointwise(const ChainArgs& c_in, const PlaneParams* inline_planes, in
                                           {"pointwise4_u8_cast_mul_sub_div_f16", "pointwise4_u8_cast_f16", "pointwise4_u8_interp_f16"}};
         static const char* by_depth[6] = {"", "pointwise4_s8", "pointwise4_u16", "pointwise4_s16", "pointwise4_s32", "pointwise4_f32"};
         info->kernel = prog_id == 3 ? by_depth[c.read.depth] : names[f16][prog_id];
+        if (bf16) info->kernel = bf16_kernel_name(info->kernel);
     }
     if (dry_run) return 1;
     hipStream_t s = (hipStream_t)stream;
@@ -497,10 +526,12 @@ int launch_pointwise(const ChainArgs& c_in, const PlaneParams* inline_planes, in
         default: e = launch_pw_depth<CVGS_DEPTH_32F>(norm, c, inline_planes, n_inline, g, s); break;
         }
     } else {
-        e = f16 ? launch_pw_cn<_Float16>(prog_id, c, inline_planes, n_inline, g, s)
+        e = bf16 ? pw_launch_bf16(prog_id, -1, c, inline_planes, n_inline, g, s)
+            : f16 ? launch_pw_cn<_Float16>(prog_id, c, inline_planes, n_inline, g, s)
                 : launch_pw_cn<float>(prog_id, c, inline_planes, n_inline, g, s);
     }
     return e == hipSuccess ? 1 : -(int)e - 1000;
 }
+#endif // CVGS_PW_BF16_TU
 
 } // namespace cvgs

@@ -28,6 +28,14 @@ __device__ __forceinline__ void store4(_Float16* p, float a, float b, float c, f
 }
 __device__ __forceinline__ void store1(float* p, float v) { *p = v; }
 __device__ __forceinline__ void store1(_Float16* p, float v) { *p = (_Float16)v; }
+// bf16 (CV_16BF): the same shape, two v_cvt_pk_bf16_f32 and one 8-byte store
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef bf16x4 bf16x4u __attribute__((aligned(2)));
+__device__ __forceinline__ void store4(__bf16* p, float a, float b, float c, float d) {
+    bf16x4 q = {(__bf16)a, (__bf16)b, (__bf16)c, (__bf16)d};
+    __builtin_nontemporal_store(q, (bf16x4u*)p);
+}
+__device__ __forceinline__ void store1(__bf16* p, float v) { *p = (__bf16)v; }
 // packed u8 pixels (the 4:2:0 read mode's `-> convertTo<CV_32FCn, CV_8UCn> -> write` chains): the chain's trailing
 // SaturateCast is the store's conversion (k_common.hpp: sat_u8_insert)
 __device__ __forceinline__ void store4(uint8_t* p, float a, float b, float c, float d) {
@@ -488,7 +496,9 @@ __device__ __forceinline__ void pw4_write(const ChainArgs& c, const PwGeom& g, c
 }
 
 // host side (k_pointwise.hip): eligibility + geometry of the thread-fused path
-// (u8out: packed u8 pixels behind a 4:2:0 read, accepted only when the caller passes the flag)
-bool pointwise4_plan(const ChainArgs& c_in, int n_inline, uint32_t chain_flags, ChainArgs& c, PwGeom& g, int& prog_id, bool& f16, bool* u8out = nullptr);
+// (u8out: packed u8 pixels behind a 4:2:0 read, accepted only when the caller passes the flag; bf16out likewise for bf16 targets, which
+// then come back with f16 = true: a 16-bit float store, *bf16out telling which)
+bool pointwise4_plan(const ChainArgs& c_in, int n_inline, uint32_t chain_flags, ChainArgs& c, PwGeom& g, int& prog_id, bool& f16, bool* u8out = nullptr,
+                     bool* bf16out = nullptr);
 
 } // namespace cvgs

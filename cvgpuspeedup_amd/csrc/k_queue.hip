@@ -1385,6 +1385,10 @@ static int queue_submit_slot(Queue* q, const ChainArgs& c_in, const PlaneParams*
     const int kind = p010 ? QK_P010 : (nv12 ? QK_NV12 : (wide ? QK_PIXELS16 : QK_PIXELS));
     const int vcn = nv12 ? r.out_cn : r.cn; // channels of the value the program sees
     const bool half = w.depth == CVGS_DEPTH_16F; // the half-precision hand-off: the chain ends with CAST(CV_16F), which the store performs
+    if (w.depth == kDepthBF16 || r.depth == kDepthBF16) { // the server's workers store fp32 / fp16 only: a bf16 chain must never reach them
+        err = "queue: CV_16BF (bf16) chains are not served by the descriptor queue (use cvgs_execute / cvgs_execute_many)";
+        return 1;
+    }
     if (!planar || (w.depth != CVGS_DEPTH_32F && !half) || w.data2 || r.table || n_planes < 1 || n_planes > kQMaxPlanes || n_planes != r.batch ||
         (!nv12 && (r.kind != CVGS_READ_RESIZE_LINEAR || (r.depth != CVGS_DEPTH_8U && !wide) || (r.cn != 3 && r.cn != 4))) ||
         (nv12 && ((r.yuv_layout != CVGS_YUV_NV12 && r.yuv_layout != CVGS_YUV_NV21 && !p010) || r.out_cn != 3))) {

@@ -417,9 +417,12 @@ __device__ __forceinline__ void st_sys(OT* p, float v) {
 __device__ __forceinline__ void st_nt(float* p, float v) { __builtin_nontemporal_store(v, p); }
 // fp16 output: the chain's trailing CAST(CV_16F) is this one round-to-nearest-even conversion
 __device__ __forceinline__ void st_nt(_Float16* p, float v) { __builtin_nontemporal_store((_Float16)v, p); }
+// bf16 output (CV_16BF): the same, one v_cvt_pk_bf16_f32 (round to nearest even, overflow to +-inf)
+__device__ __forceinline__ void st_nt(__bf16* p, float v) { __builtin_nontemporal_store((__bf16)v, p); }
 
 __device__ __forceinline__ void st_plain(float* p, float v) { __builtin_nontemporal_store(v, p); }
 __device__ __forceinline__ void st_plain(_Float16* p, float v) { __builtin_nontemporal_store((_Float16)v, p); }
+__device__ __forceinline__ void st_plain(__bf16* p, float v) { __builtin_nontemporal_store((__bf16)v, p); }
 // u8 targets: the chain's trailing SaturateCast (round to nearest even, clamp, NaN -> 0) is this conversion
 __device__ __forceinline__ void st_plain(uint8_t* p, float v) { __builtin_nontemporal_store((uint8_t)sat_u8_insert(v, 0, 0), p); }
 // 16-bit integer targets (the reference's resize -> convertTo<32F, 16U / 16S> -> write chains, tests/resize/test_resize_write.cu)
@@ -471,6 +474,19 @@ __device__ __forceinline__ void store_packed_px(OT* px, const float* v, int cn) 
                 __builtin_nontemporal_store(hi, (vh2u*)(px + 2));
             } else {
                 __builtin_nontemporal_store((_Float16)v[2], px + 2);
+            }
+            return;
+        } else if constexpr (std::is_same_v<OT, __bf16>) {
+            // the fp16 branch's store shape: each pair is one v_cvt_pk_bf16_f32 and one 32-bit store
+            typedef __bf16 vb2 __attribute__((ext_vector_type(2)));
+            typedef vb2 vb2u __attribute__((aligned(2)));
+            vb2 lo = {(__bf16)v[0], (__bf16)v[1]};
+            __builtin_nontemporal_store(lo, (vb2u*)px);
+            if constexpr (CN == 4) {
+                vb2 hi = {(__bf16)v[2], (__bf16)v[3]};
+                __builtin_nontemporal_store(hi, (vb2u*)(px + 2));
+            } else {
+                __builtin_nontemporal_store((__bf16)v[2], px + 2);
             }
             return;
         } else if constexpr (sizeof(OT) == 2) { // 16-bit integers: pairs of elements as one 32-bit store

@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void k_warp(const WarpKernArgs<NPL> a, const W
     }
     InterpProgInt::run(c.prog, p, depth, cn);
     const DstPlane* dst = c.write.table ? c.write.table : c.dst_inline;
-    write_px(c.write, dst, x, y, z, p, depth, cn);
+    write_px<true>(c.write, dst, x, y, z, p, depth, cn);
 }
 
 template <int NPL>
@@ -228,6 +228,14 @@ static hipError_t launch_warp_fast_prog(bool f16, int prog_id, const ChainArgs& 
     return launch_warp_fast_ot<CN, PERSP, float>(prog_id, c, planes, n, table, s);
 }
 
+// bf16 (CV_16BF) tensors: the fp16 instantiations' twins with OT = __bf16, compiled in k_warp_bf16.hip (this file with CVGS_WARP_BF16_TU)
+hipError_t warp_fast_launch_bf16(int cn, bool persp, int prog_id, const ChainArgs& c, const WarpPlane* planes, int n, const WarpPlane* table, hipStream_t s);
+#ifdef CVGS_WARP_BF16_TU
+hipError_t warp_fast_launch_bf16(int cn, bool persp, int prog_id, const ChainArgs& c, const WarpPlane* planes, int n, const WarpPlane* table, hipStream_t s) {
+    if (cn == 3) return persp ? launch_warp_fast_ot<3, true, __bf16>(prog_id, c, planes, n, table, s) : launch_warp_fast_ot<3, false, __bf16>(prog_id, c, planes, n, table, s);
+    return persp ? launch_warp_fast_ot<4, true, __bf16>(prog_id, c, planes, n, table, s) : launch_warp_fast_ot<4, false, __bf16>(prog_id, c, planes, n, table, s);
+}
+#else
 // 1 = took it, 0 = not eligible
 static int try_warp_fast(const ChainArgs& c_in, const WarpPlane* planes, int n, const WarpPlane* table, hipStream_t s, bool dry_run,
                          LaunchInfo* info, hipError_t* err) {
@@ -236,7 +244,9 @@ static int try_warp_fast(const ChainArgs& c_in, const WarpPlane* planes, int n, 
     const bool planar = c_in.write.kind == CVGS_WRITE_TENSOR_SPLIT || c_in.write.kind == CVGS_WRITE_TENSOR_T_SPLIT;
     const bool packed = c_in.write.kind == CVGS_WRITE_PIXEL_2D || c_in.write.kind == CVGS_WRITE_PIXEL_3D;
     if ((!planar && !packed) || c_in.write.data2) return 0;
-    const bool f16 = c_in.write.depth == CVGS_DEPTH_16F;
+    // bf16 tensors take the fp16 path with the bf16 twins ("f16" below: a 16-bit float store); the program may hold no other bf16 cast
+    const bool bf16 = c_in.write.depth == kDepthBF16;
+    const bool f16 = c_in.write.depth == CVGS_DEPTH_16F || bf16;
     if (!f16 && c_in.write.depth != CVGS_DEPTH_32F) return 0;
     if (packed && f16) return 0;
     ChainArgs c_cut;
@@ -271,11 +281,16 @@ static int try_warp_fast(const ChainArgs& c_in, const WarpPlane* planes, int n, 
         static const char* names_packed[2][2] = {{"warp_affine_u8c3_packed_f32", "warp_affine_u8c4_packed_f32"},
                                                  {"warp_perspective_u8c3_packed_f32", "warp_perspective_u8c4_packed_f32"}};
         info->kernel = packed ? names_packed[persp][r.cn == 4] : (f16 ? names16[persp][r.cn == 4][prog_id] : names[persp][r.cn == 4][prog_id]);
+        if (bf16) info->kernel = bf16_kernel_name(info->kernel);
     }
     if (dry_run) return 1;
     if (packed) {
         if (r.cn == 3) *err = persp ? launch_warp_fast_packed<3, true>(c, planes, n, table, s) : launch_warp_fast_packed<3, false>(c, planes, n, table, s);
         else *err = persp ? launch_warp_fast_packed<4, true>(c, planes, n, table, s) : launch_warp_fast_packed<4, false>(c, planes, n, table, s);
+        return 1;
+    }
+    if (bf16) {
+        *err = warp_fast_launch_bf16(r.cn, persp, prog_id, c, planes, n, table, s);
         return 1;
     }
     if (r.cn == 3) *err = persp ? launch_warp_fast_prog<3, true>(f16, prog_id, c, planes, n, table, s) : launch_warp_fast_prog<3, false>(f16, prog_id, c, planes, n, table, s);
@@ -297,5 +312,6 @@ int launch_warp(const ChainArgs& c, const WarpPlane* planes, int n, const WarpPl
     else e = launch_warp_t<kInlineWarp>(c, planes, n, nullptr, s);
     return e == hipSuccess ? 0 : -(int)e - 1000;
 }
+#endif // CVGS_WARP_BF16_TU
 
 } // namespace cvgs

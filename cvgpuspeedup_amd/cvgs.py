@@ -11,8 +11,8 @@ import ctypes as C
 import struct
 
 from . import capi
-from .capi import (DEPTH_8U, DEPTH_8S, DEPTH_16U, DEPTH_16S, DEPTH_32S, DEPTH_32F, DEPTH_64F, DEPTH_16F, make_type,
-                   type_cn, type_depth)
+from .capi import (DEPTH_8U, DEPTH_8S, DEPTH_16U, DEPTH_16S, DEPTH_32S, DEPTH_32F, DEPTH_64F, DEPTH_16F, DEPTH_16BF, make_type,
+                   type_cn, type_depth, type_is_bf16, cast_aux)
 
 # ---- OpenCV type codes / enums (numeric values of OpenCV 4.x) ---------------------------------------
 for _d, _n in ((DEPTH_8U, "8U"), (DEPTH_8S, "8S"), (DEPTH_16U, "16U"), (DEPTH_16S, "16S"), (DEPTH_32S, "32S"),
@@ -20,6 +20,10 @@ for _d, _n in ((DEPTH_8U, "8U"), (DEPTH_8S, "8S"), (DEPTH_16U, "16U"), (DEPTH_16
     globals()["CV_" + _n] = _d
     for _c in (1, 2, 3, 4):
         globals()["CV_%sC%d" % (_n, _c)] = make_type(_d, _c)
+# CV_16BF: the bfloat16 hand-off type, CV_16FCn with the bf16 flag (include/cvgs_hip.h)
+CV_16BF = DEPTH_16BF
+for _c in (1, 2, 3, 4):
+    globals()["CV_16BFC%d" % _c] = make_type(DEPTH_16F, _c) | capi.TYPE_FLAG_BF16
 
 INTER_LINEAR = 1
 COLOR_BGR2BGRA = COLOR_RGB2RGBA = 0
@@ -63,8 +67,10 @@ class GpuMat:
 
     @staticmethod
     def from_tensor(t, cv_type):
-        """Wrap a torch tensor (H,W[,C]) whose rows are contiguous."""
+        """Wrap a torch tensor (H,W[,C]) whose rows are contiguous (torch.bfloat16 tensors: CV_16BF types)."""
         assert t.stride(-1) == 1 or t.dim() == 2
+        if str(t.dtype) == "torch.bfloat16" and not type_is_bf16(cv_type):
+            raise ValueError("a torch.bfloat16 tensor holds CV_16BF elements")
         return GpuMat(t.shape[0], t.shape[1], cv_type, t.data_ptr(), t.stride(0) * t.element_size(), owner=t)
 
     @staticmethod
@@ -236,7 +242,7 @@ def cast(in_type, out_type):
     (tests/warping/test_warping_opencv.cu:63)."""
     if type_cn(in_type) != type_cn(out_type):
         raise ValueError("Cast cannot change the number of channels")
-    return PointwiseIOp(in_type, out_type, [(capi.OP_CAST_TRUNC, type_depth(out_type), None)])
+    return PointwiseIOp(in_type, out_type, [(capi.OP_CAST_TRUNC, cast_aux(out_type), None)])
 
 
 def read_nv12(mat, dsize=None, color_range=capi.YUV_FULL, primaries=capi.BT709, alpha=True, layout=capi.YUV_NV12):
@@ -257,11 +263,11 @@ def convertTo(in_type, out_type, alpha=None, beta=None):
     through float: cast -> mul -> (add) -> saturate."""
     if type_cn(in_type) != type_cn(out_type):
         raise ValueError("convertTo does not support changing the number of channels")
-    od = type_depth(out_type)
+    od = cast_aux(out_type)
     if alpha is None:
         return PointwiseIOp(in_type, out_type, [(capi.OP_CAST, od, None)])
-    # CV_16F (this engine's half hand-off type) is storage only: computed in float, rounded once at the end
-    integral = od in (DEPTH_8U, DEPTH_8S, DEPTH_16U, DEPTH_16S, DEPTH_32S, DEPTH_16F)
+    # CV_16F / CV_16BF (this engine's 16-bit float hand-off types) are storage only: computed in float, rounded once at the end
+    integral = od in (DEPTH_8U, DEPTH_8S, DEPTH_16U, DEPTH_16S, DEPTH_32S, DEPTH_16F, DEPTH_16BF)
     mid = DEPTH_32F if integral else od  # float for integral outputs, the output type (32F / 64F) otherwise
     f32 = lambda v: struct.unpack("f", struct.pack("f", float(v)))[0]  # the reference's parameters are `float`
     ops = [(capi.OP_CAST, mid, None), (capi.OP_MUL, 0, [f32(alpha)] * 4)]

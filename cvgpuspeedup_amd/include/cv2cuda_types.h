@@ -21,6 +21,7 @@ template <> struct depth_base<CV_32S> { using type = int; };
 template <> struct depth_base<CV_32F> { using type = float; };
 template <> struct depth_base<CV_64F> { using type = double; };
 template <> struct depth_base<CV_16F> { using type = cvgs::half_t; }; // engine extension: half-precision hand-off
+template <> struct depth_base<CV_16BF> { using type = cvgs::bfloat16_t; }; // engine extension: the bfloat16 hand-off (CV_16F | bf16 flag)
 
 // scalar for one channel, HIP_vector_type<base, N> otherwise (uchar3, float4, ...)
 template <typename B, int CN> struct vec_of { using type = HIP_vector_type<B, CN>; };
@@ -31,7 +32,7 @@ template <int CV_TYPE>
 struct cv2cuda_t {
     static_assert(CV_MAT_CN(CV_TYPE) >= 1 && CV_MAT_CN(CV_TYPE) <= 4 && CV_MAT_DEPTH(CV_TYPE) <= CV_16F,
                   "unsupported OpenCV type code");
-    using base = typename detail::depth_base<CV_MAT_DEPTH(CV_TYPE)>::type;
+    using base = typename detail::depth_base<CV_MAT_DEPTH(CV_TYPE) | (CV_TYPE & 0x1000)>::type; // (CV_16BF keeps its flag)
     using type = typename detail::vec_of<base, CV_MAT_CN(CV_TYPE)>::type;
 };
 
@@ -56,9 +57,11 @@ template <> struct base_depth<uint> { static constexpr int value = CV_32S; };
 template <> struct base_depth<float> { static constexpr int value = CV_32F; };
 template <> struct base_depth<double> { static constexpr int value = CV_64F; };
 template <> struct base_depth<cvgs::half_t> { static constexpr int value = CV_16F; };
+template <> struct base_depth<cvgs::bfloat16_t> { static constexpr int value = CV_16BF; };
 
 template <typename T>
-constexpr int cv_type_of = CV_MAKETYPE(base_depth<typename vector_traits<T>::base>::value, vector_traits<T>::cn);
+constexpr int cv_type_of = CV_MAKETYPE(base_depth<typename vector_traits<T>::base>::value, vector_traits<T>::cn) |
+                           (base_depth<typename vector_traits<T>::base>::value & 0x1000); // (CV_MAKETYPE masks the bf16 flag away)
 
 // --- supported-code lists (reference include/cv2cuda_types.cuh:63-92) -------------------------------
 template <int... CODES> struct CodesList {};
@@ -77,4 +80,4 @@ template <int CODE> constexpr bool isSupportedInterpolation = one_of_c<CODE, Sup
 } // namespace cvGS
 
 #define CUDA_T(CV_TYPE) typename cvGS::cv2cuda_t<CV_TYPE>::type
-#define BASE_CUDA_T(CV_TYPE) typename cvGS::cv2cuda_t<CV_MAT_DEPTH(CV_TYPE)>::type
+#define BASE_CUDA_T(CV_TYPE) typename cvGS::cv2cuda_t<CV_MAT_DEPTH(CV_TYPE) | ((CV_TYPE) & 0x1000)>::type

@@ -64,7 +64,7 @@ namespace internal {
 template <int I, int O>
 inline auto convertToScaled(float alpha, const float* beta) {
     static_assert(CV_MAT_CN(I) == CV_MAT_CN(O), "convertTo does not support changing the number of channels, neither in cvGS nor in OpenCV. Please, use cvGS::cvtColor instead.");
-    constexpr bool integral = CV_MAT_DEPTH(O) <= CV_32S || CV_MAT_DEPTH(O) == CV_16F; // CV_16F: storage only, rounded once
+    constexpr bool integral = CV_MAT_DEPTH(O) <= CV_32S || CV_MAT_DEPTH(O) == CV_16F; // CV_16F / CV_16BF: storage only, rounded once
     constexpr int mid = integral ? CV_32F : CV_MAT_DEPTH(O);
     fk::PointwiseSeq<CUDA_T(I), CUDA_T(O)> seq;
     fk::ChainBuilder b;
@@ -75,7 +75,7 @@ inline auto convertToScaled(float alpha, const float* beta) {
         const float bb[4] = {*beta, *beta, *beta, *beta};
         b.op(CVGS_OP_ADD, 0, bb);
     }
-    if (integral) b.op(CVGS_OP_CAST, CV_MAT_DEPTH(O));
+    if (integral) b.op(CVGS_OP_CAST, CV_MAT_DEPTH(O) | (O & 0x1000)); // (CV_16BF: CVGS_DEPTH_16BF)
     seq.ops.assign(b.d.ops, b.d.ops + b.d.n_ops);
     return seq;
 }

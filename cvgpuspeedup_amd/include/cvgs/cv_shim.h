@@ -15,11 +15,13 @@
 #include <opencv2/core/cuda.hpp>
 #include <opencv2/core/cuda_stream_accessor.hpp>
 #include <opencv2/imgproc.hpp>
+#include "bfloat16.h"
 #else
 
 #include <hip/hip_runtime_api.h>
 
 #include "half.h"
+#include "bfloat16.h"
 
 #include <cmath>
 #include <cstdint>
@@ -434,3 +436,12 @@ private:
 } // namespace cv
 
 #endif // CVGS_USE_OPENCV
+
+// CV_16BF (engine extension: the bfloat16 hand-off): CV_16FCn with the engine's bf16 flag, bit 12 (CVGS_TYPE_FLAG_BF16, include/cvgs_hip.h).
+// Spelled with the flag, not with CV_MAKETYPE, which masks the depth.  Under real OpenCV, GpuMat::create strips bit 12:
+// the GpuMat then reads CV_16FCn, the same bytes, and the bf16 marker lives in the IOps' template arguments.
+#ifndef CV_16BF
+#define CV_16BF (CV_16F | 0x1000)
+constexpr int CV_16BFC1 = CV_MAKETYPE(CV_16F, 1) | 0x1000, CV_16BFC2 = CV_MAKETYPE(CV_16F, 2) | 0x1000, CV_16BFC3 = CV_MAKETYPE(CV_16F, 3) | 0x1000,
+              CV_16BFC4 = CV_MAKETYPE(CV_16F, 4) | 0x1000;
+#endif

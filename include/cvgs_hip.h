@@ -66,7 +66,15 @@ typedef enum cvgs_status {
  * CV_16F (IEEE binary16) is this engine's half-precision hand-off option (the reference has no
  * half type): a storage format only -- per-pixel read source, CAST target (round-to-nearest-even, overflow to
  * +-inf, like cv::saturate_cast<cv::float16_t>) and write type; arithmetic stages need a CAST to CV_32F (or CV_64F) first;
- * a CV_64F value becomes CV_16F through float (two roundings, like the double -> float -> half conversion it spells).   */
+ * a CV_64F value becomes CV_16F through float (two roundings, like the double -> float -> half conversion it spells).
+ * CV_16BF (bfloat16) is the second 16-bit float hand-off, for networks that run in bf16.  OpenCV's 3-bit depth field is
+ * full, so it is spelled as depth 16F plus CVGS_TYPE_FLAG_BF16 (bit 12: outside OpenCV 4's CV_MAT_TYPE_MASK 0xFFF and below
+ * its CONT / SUBMAT flags).  CVGS_TYPE_DEPTH still reads 7 (2 bytes per element) and CVGS_TYPE_CN masks the bit away.  It is
+ * a storage format with CV_16F's contract, wherever CV_16F is accepted: per-pixel / resize / warp read source (widened to
+ * fp32 exactly), CAST / CAST_TRUNC target (aux = CVGS_DEPTH_16BF; computed in fp32 and rounded once to nearest even,
+ * overflow to +-inf, +-0, subnormals and infinities kept; a NaN stays a NaN, its sign and payload are unspecified; integer,
+ * CV_64F (through float: two roundings) and CV_16F values get there through float) and write type.  Arithmetic stages and
+ * GRAY on CV_16BF values: CVGS_ERR_UNSUPPORTED.  Other bits above the channel field keep their meaning (none).            */
 #define CVGS_DEPTH_8U 0
 #define CVGS_DEPTH_8S 1
 #define CVGS_DEPTH_16U 2
@@ -78,6 +86,9 @@ typedef enum cvgs_status {
 #define CVGS_MAKETYPE(depth, cn) ((depth) + (((cn) - 1) << 3))
 #define CVGS_TYPE_DEPTH(t) ((t) & 7)
 #define CVGS_TYPE_CN(t) ((((t) >> 3) & 63) + 1)
+#define CVGS_TYPE_FLAG_BF16 0x1000                            /* with depth 16F: the 16-bit float is bfloat16 */
+#define CVGS_DEPTH_16BF (CVGS_DEPTH_16F | CVGS_TYPE_FLAG_BF16) /* also a valid CAST / CAST_TRUNC aux            */
+#define CVGS_TYPE_IS_BF16(t) (((t) & CVGS_TYPE_FLAG_BF16) != 0)
 
 /* A pitched 2D image view: replaces fk::RawPtr<fk::_2D,T> / fk::Ptr2D<T> as produced by
  * gpuMat2RawPtr2D / gpuMat2Ptr2D (reference include/cvGPUSpeedup.cuh:34-44).  A crop is a view:

@@ -56,6 +56,7 @@ READ_PIXEL, READ_RESIZE_LINEAR, READ_NV12, READ_NV12_RESIZE_LINEAR, READ_WARP_AF
 PRESERVE_AR, IGNORE_AR, PRESERVE_AR_RN_EVEN, PRESERVE_AR_LEFT = 0, 1, 2, 3
 YUV_FULL, YUV_LIMITED = 0, 1
 YUV_NV12, YUV_NV21, YUV_I420, YUV_YV12, YUV_P010 = 0, 1, 2, 3, 4
+YUV_YUYV, YUV_UYVY = 5, 6  # packed 4:2:2: bytes Y0 U Y1 V / U Y0 V Y1 per pixel pair (CV_8UC2 surfaces)
 BT601, BT709, BT2020 = 0, 1, 2
 READ_FLAG_TABLE_ON_DEVICE = 1
 READ_FLAG_TABLE_SOURCES_VOUCHED = 2

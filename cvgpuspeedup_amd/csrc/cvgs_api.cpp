@@ -69,6 +69,7 @@ int cast_depth(int aux) {
 bool is_resize(int kind) { return kind == CVGS_READ_RESIZE_LINEAR || kind == CVGS_READ_NV12_RESIZE_LINEAR; }
 constexpr int kMaxDim = CVGS_MAX_DIM; // widest / tallest plane the 32-bit index arithmetic of the kernels is specified for
 bool is_nv12(int kind) { return kind == CVGS_READ_NV12 || kind == CVGS_READ_NV12_RESIZE_LINEAR; }
+bool is_yuv422(int layout) { return layout == CVGS_YUV_YUYV || layout == CVGS_YUV_UYVY; } // packed 4:2:2: one plane of 4-byte pixel pairs
 bool is_warp(int kind) { return kind == CVGS_READ_WARP_AFFINE || kind == CVGS_READ_WARP_PERSPECTIVE; }
 
 // Host half of fk::Resize::build: the kernel-side scale factors and the aspect-ratio window.
@@ -215,11 +216,13 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
     // CV_64F / CV_16F / CV_16BF sources: per-pixel reads and the bilinear resize (taps are cast to float, the output is CV_32F, reference
     // include/cvGPUSpeedup.cuh:227); CV_16F / CV_16BF also as a warp source.  A CV_64F warp source has no kernel.
     if (is_nv12(rd.kind)) {
-        if (rd.yuv_layout < CVGS_YUV_NV12 || rd.yuv_layout > CVGS_YUV_P010) return fail(CVGS_ERR_INVALID, "bad yuv_layout");
+        if (rd.yuv_layout < CVGS_YUV_NV12 || rd.yuv_layout > CVGS_YUV_UYVY) return fail(CVGS_ERR_INVALID, "bad yuv_layout");
         if (rd.yuv_range < CVGS_YUV_FULL || rd.yuv_range > CVGS_YUV_LIMITED) return fail(CVGS_ERR_INVALID, "bad yuv_range");
         if (rd.yuv_primaries < CVGS_BT601 || rd.yuv_primaries > CVGS_BT2020) return fail(CVGS_ERR_INVALID, "bad yuv_primaries");
         if (rd.yuv_layout == CVGS_YUV_P010) {
             if (rd.src_type != CVGS_MAKETYPE(CVGS_DEPTH_16U, 1)) return fail(CVGS_ERR_INVALID, "P010 reads need a CV_16UC1 source");
+        } else if (is_yuv422(rd.yuv_layout)) {
+            if (rd.src_type != CVGS_MAKETYPE(CVGS_DEPTH_8U, 2)) return fail(CVGS_ERR_INVALID, "YUYV / UYVY reads need a CV_8UC2 source");
         } else if (rd.src_type != CVGS_MAKETYPE(CVGS_DEPTH_8U, 1))
             return fail(CVGS_ERR_INVALID, "NV12 reads need a CV_8UC1 source");
     }
@@ -244,7 +247,7 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
     // layouts (2-byte alignment, even steps, whole surfaces: checked below for HOST descriptors only) cannot be checked on a
     // table this call cannot read -- a table built for NV12 and executed as I420 would address a second chroma plane that is not there
     if (table && is_nv12(rd.kind) && rd.yuv_layout != CVGS_YUV_NV12 && rd.yuv_layout != CVGS_YUV_NV21)
-        return fail(CVGS_ERR_UNSUPPORTED, "device plane tables serve the NV12 / NV21 layouts only (P010 / I420 / YV12: host descriptors)");
+        return fail(CVGS_ERR_UNSUPPORTED, "device plane tables serve the NV12 / NV21 layouts only (P010 / I420 / YV12 / YUYV / UYVY: host descriptors)");
 
     // ---- read stage ----
     ReadArgs& R = L.args.read;
@@ -309,14 +312,20 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
             if (im.width > kMaxDim || im.height > kMaxDim) return fail(CVGS_ERR_UNSUPPORTED, "source plane wider or taller than 2^24 pixels");
             const int esz = depth_bytes(sdepth) * scn;
             if (im.step < im.width * esz) return fail(CVGS_ERR_INVALID, "source step smaller than a row");
-            if (is_nv12(rd.kind) && ((im.width & 1) || (im.height & 1)))
+            const bool p422 = is_nv12(rd.kind) && is_yuv422(rd.yuv_layout);
+            if (is_nv12(rd.kind) && !p422 && ((im.width & 1) || (im.height & 1)))
                 return fail(CVGS_ERR_INVALID, "NV12 planes need even dimensions");
             PlaneParams& P = L.planes[(size_t)z];
             P.data = (const uint8_t*)im.data;
             P.w = im.width;
             P.h = im.height;
             P.step = im.step;
-            if (is_nv12(rd.kind)) {
+            if (p422) { // one plane of 4-byte pixel pairs (odd widths and heights are fine: the last pair is read whole)
+                if (im.uv_offset) return fail(CVGS_ERR_INVALID, "YUYV / UYVY surfaces have one plane: uv_offset must be 0");
+                if (((uintptr_t)im.data | (uintptr_t)im.step) & 3) return fail(CVGS_ERR_INVALID, "YUYV / UYVY surfaces need data and step that are multiples of 4");
+                if ((int64_t)im.step < 4 * (((int64_t)im.width + 1) / 2)) return fail(CVGS_ERR_INVALID, "source step smaller than a row of whole pixel pairs");
+                P.uv_off = 0;
+            } else if (is_nv12(rd.kind)) {
                 if (im.uv_offset < 0 || (im.uv_offset & 1)) return fail(CVGS_ERR_INVALID, "NV12 uv_offset must be even and non-negative");
                 if (rd.yuv_layout == CVGS_YUV_P010 && (((uintptr_t)im.data | (uintptr_t)im.step | (uintptr_t)im.uv_offset) & 1))
                     return fail(CVGS_ERR_INVALID, "P010 surfaces need 2-byte aligned data, step and uv_offset");
@@ -1023,9 +1032,10 @@ static void source_range(const cvgs_chain_desc& c, const cvgs_image2d& im, size_
     // un-fused such launches)
     const uint8_t* lo = (const uint8_t*)im.data;
     const size_t rows = (size_t)(im.height > 0 ? im.height : 1);
-    const size_t last_row = (size_t)(im.width > 0 ? im.width : 1) * px_bytes;
+    const bool p422 = yuv && is_yuv422(c.read.yuv_layout); // packed 4:2:2: whole 4-byte pixel pairs, no chroma plane
+    const size_t last_row = p422 ? 4 * (((size_t)(im.width > 0 ? im.width : 1) + 1) / 2) : (size_t)(im.width > 0 ? im.width : 1) * px_bytes;
     const uint8_t* hi = lo + (size_t)im.step * (rows - 1) + last_row;
-    if (yuv) {
+    if (yuv && !p422) {
         // 4:2:0 surfaces: the chroma rows are read too -- behind the luma rows (whole surfaces: height * 3 / 2 rows) or,
         // for a crop view, uv_offset bytes from its first luma byte (+ half the crop's rows).  Planar chroma (I420 / YV12: two
         // quarter planes behind the luma plane) stays inside the same height * 3 / 2 rows.
@@ -1159,7 +1169,8 @@ int execute_many(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream) {
         const bool k1_u8 = chains[0].read.kind == CVGS_READ_RESIZE_LINEAR && CVGS_TYPE_CN(chains[0].read.src_type) >= 3 &&
                            CVGS_TYPE_DEPTH(chains[0].read.src_type) == CVGS_DEPTH_8U;
         const bool k4_il = chains[0].read.kind == CVGS_READ_NV12_RESIZE_LINEAR &&
-                           (chains[0].read.yuv_layout == CVGS_YUV_NV12 || chains[0].read.yuv_layout == CVGS_YUV_NV21 || chains[0].read.yuv_layout == CVGS_YUV_P010); // interleaved chroma
+                           (chains[0].read.yuv_layout == CVGS_YUV_NV12 || chains[0].read.yuv_layout == CVGS_YUV_NV21 || chains[0].read.yuv_layout == CVGS_YUV_P010 ||
+                            is_yuv422(chains[0].read.yuv_layout)); // interleaved chroma / packed 4:2:2
         if (!tables0 && inline_ok && (k1_u8 || k4_il)) {
             size_t planes = 0;
             for (int i = 0; i < n; ++i) planes += (size_t)(chains[i].read.batch > 0 ? chains[i].read.batch : 0);
@@ -1755,7 +1766,7 @@ static int queue_submit_one(cvgs_queue_t h, const cvgs_chain_desc* chain, uint64
     Lowered L;
     int rc = lower(chain, false, L);
     if (rc) return rc;
-    if (L.uses_64f || L.int_arith || L.mirrors.n > 0 || is_warp(L.args.read.kind) || (chain->flags & CVGS_CHAIN_FORCE_GENERIC))
+    if (L.uses_64f || L.int_arith || L.mirrors.n > 0 || is_warp(L.args.read.kind) || is_yuv422(L.args.read.yuv_layout) || (chain->flags & CVGS_CHAIN_FORCE_GENERIC))
         return fail(CVGS_ERR_UNSUPPORTED, "queue: not a chain the server takes");
     std::string err;
     rc = cvgs::queue_submit(h->q, L.args, L.planes.data(), (int)L.planes.size(), ticket, err);
@@ -1793,7 +1804,7 @@ int cvgs_queue_submit_on(cvgs_queue_t h, const cvgs_chain_desc* chain, cvgs_stre
     const bool hybrid = (flags & CVGS_QUEUE_SUBMIT_HYBRID) != 0;
     std::string err;
     rc = 1;
-    if (!(L.uses_64f || L.int_arith || L.mirrors.n > 0 || is_warp(L.args.read.kind) || (chain->flags & CVGS_CHAIN_FORCE_GENERIC))) {
+    if (!(L.uses_64f || L.int_arith || L.mirrors.n > 0 || is_warp(L.args.read.kind) || is_yuv422(L.args.read.yuv_layout) || (chain->flags & CVGS_CHAIN_FORCE_GENERIC))) {
         const cvgs::ChainArgs* ca = &L.args;
         const cvgs::PlaneParams* pp = L.planes.data();
         const int np = (int)L.planes.size();
@@ -1836,7 +1847,7 @@ int cvgs_queue_submit_many_on(cvgs_queue_t h, const cvgs_chain_desc* const* chai
     for (int32_t i = 0; i < n; ++i) {
         if (int rc = lower(chains[i], false, L[(size_t)i])) return rc;
         const Lowered& l = L[(size_t)i];
-        servable = servable && !(l.uses_64f || l.int_arith || l.mirrors.n > 0 || is_warp(l.args.read.kind) || (chains[i]->flags & CVGS_CHAIN_FORCE_GENERIC));
+        servable = servable && !(l.uses_64f || l.int_arith || l.mirrors.n > 0 || is_warp(l.args.read.kind) || is_yuv422(l.args.read.yuv_layout) || (chains[i]->flags & CVGS_CHAIN_FORCE_GENERIC));
     }
     std::string err = "queue: not chains the server takes";
     int rc = 1, queued = 0;

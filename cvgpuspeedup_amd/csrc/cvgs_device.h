@@ -224,6 +224,9 @@ int launch_nv12(const ChainArgs& c, const PlaneParams* inline_planes, int n_inli
 int launch_nv12_x2(const ChainArgs& c, const PlaneParams* planes, int n_planes, bool prog_swap, void* stream, bool dry_run);
 static constexpr int64_t kK4X2MinWaveRows = 4096; // output rows x 64-column tiles x surfaces from which launch_nv12 prefers it
 bool k4_planes_eligible(const PlaneParams* planes, int n, int dst_w, int dst_h);
+// Packed 4:2:2 surfaces (YUYV / UYVY) read back inside the bilinear resize (k_yuv422.hip): K4's targets and dispatch rules; launch_nv12
+// forwards the two layouts here, so every caller of launch_nv12 serves them.  1 launched / 0 not eligible / < 0 error.
+int launch_yuv422(const ChainArgs& c, const PlaneParams* inline_planes, int n_inline, LaunchCtx& ctx, bool dry_run, LaunchInfo* info);
 
 // Thread-fused pointwise chains on u8 sources (4 pixels per thread) -> fp32 planar / packed.
 // n_segs chains of ONE thread-fused pointwise shape (per-pixel reads of u8 planes -> fp32 tensor / packed fp32 pixels) in one launch: the

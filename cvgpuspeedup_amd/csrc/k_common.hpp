@@ -603,6 +603,12 @@ __device__ __forceinline__ void nv12_px(const PlaneParams& P, int x, int y, cons
         Y = (float)(yrow[x] >> 6);
         U = (float)(uv[0] >> 6);
         V = (float)(uv[1] >> 6);
+    } else if (k.layout >= CVGS_YUV_YUYV) { // packed 4:2:2: Y0 U Y1 V (YUYV) or U Y0 V Y1 (UYVY) per pixel pair, chroma on every row
+        const uint8_t* pr = P.data + (size_t)y * P.step + 4 * (size_t)(x >> 1);
+        const int uy = k.layout == CVGS_YUV_UYVY ? 1 : 0;
+        Y = (float)pr[2 * (x & 1) + uy];
+        U = (float)pr[1 - uy];
+        V = (float)pr[3 - uy];
     } else if (k.layout <= CVGS_YUV_NV21) { // interleaved chroma: one (U,V) or (V,U) pair per 2x2 luma block
         const uint8_t* uv = P.data + (size_t)P.uv_off + (size_t)(y >> 1) * P.step + 2 * (x >> 1);
         Y = (float)P.data[(size_t)y * P.step + x];

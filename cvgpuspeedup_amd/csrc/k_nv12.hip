@@ -551,6 +551,8 @@ int launch_nv12(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_i
     const int n_segs = ctx.n_segs;
     void* const stream = ctx.stream;
     const ReadArgs& r = c_in.read;
+    if (r.yuv_layout == CVGS_YUV_YUYV || r.yuv_layout == CVGS_YUV_UYVY) // packed 4:2:2: its own kernel family (k_yuv422.hip), any plane width
+        return launch_yuv422(c_in, inline_planes, n_inline, ctx, dry_run, info);
     // fp16 / bf16 planar tensors: the trailing CAST(CV_16F / CV_16BF) moves into the store (a bf16 chain of any other shape: the
     // interpreted kernel); "f16" below means "a 16-bit float store" from here on
     const bool planar_kind = c_in.write.kind == CVGS_WRITE_TENSOR_SPLIT || c_in.write.kind == CVGS_WRITE_TENSOR_T_SPLIT;

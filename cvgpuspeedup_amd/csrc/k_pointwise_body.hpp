@@ -161,7 +161,8 @@ __device__ __forceinline__ float elem_value(const uint32_t* raw, int e) {
 // pseudo source depths of pw4_body: 4:2:0 decoder surfaces with interleaved chroma read WITHOUT a resize (CVGS_READ_NV12; NV12 /
 // NV21 8-bit samples, P010 16-bit samples) -- the pixel arrives as CV_32F R, G, B[, A] through k_common.hpp's yuv_to_rgb
 constexpr int SD_NV12 = 64, SD_P010 = 65, SD_I420 = 66; // SD_I420: planar chroma (I420 / YV12: two quarter-size planes behind the luma)
-template <int SD> constexpr bool is_yuv_sd = SD == SD_NV12 || SD == SD_P010 || SD == SD_I420;
+constexpr int SD_YUV422 = 67; // packed 4:2:2 (YUYV / UYVY): one plane of 4-byte pixel pairs, chroma on every row
+template <int SD> constexpr bool is_yuv_sd = SD == SD_NV12 || SD == SD_P010 || SD == SD_I420 || SD == SD_YUV422;
 template <int SD> constexpr int src_elem_bytes = (SD == CVGS_DEPTH_8U || SD == CVGS_DEPTH_8S) ? 1 : ((SD == CVGS_DEPTH_16U || SD == CVGS_DEPTH_16S) ? 2 : 4);
 
 // The thread's 4 work pixels travel to the write stage BY VALUE.  Round 2 passed `const Px (&)[4]`: after inlining, LLVM kept
@@ -262,6 +263,25 @@ __device__ __forceinline__ void pw4_body(const ChainArgs& c, const PlaneParams& 
         Px px[4];
         int depth = CVGS_DEPTH_32F, cn = CN;
         if (z < used) {
+            if constexpr (SD == SD_YUV422) {
+                // packed 4:2:2: the thread's 4 pixels are two pixel pairs = 8 bytes at 2 * x0 of a 4-byte aligned row; a ragged tail reads
+                // whole pairs (the bytes a plane may read: [0, 4 * ceil(w / 2)) of each row) and nothing behind them
+                const gp_u8 prow = (gp_u8)P.data + (size_t)y * (size_t)P.step + (size_t)x0 * 2;
+                uint32_t q[2];
+                q[0] = *(gp_u32)prow;
+                q[1] = npx > 2 ? *(gp_u32)(prow + 4) : 0u;
+                if (c.read.yuv_layout == CVGS_YUV_UYVY) { // wave-uniform: swap the bytes of every 16-bit half, then everything below is YUYV
+                    q[0] = __builtin_amdgcn_perm(q[0], q[0], 0x02030001u);
+                    q[1] = __builtin_amdgcn_perm(q[1], q[1], 0x02030001u);
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const uint32_t w = q[i >> 1];
+                    yuv_to_rgb((float)((w >> (16 * (i & 1))) & 0xffu), (float)((w >> 8) & 0xffu), (float)(w >> 24), yk, px[i]);
+#pragma unroll
+                    for (int ch = CN; ch < 4; ++ch) px[i].v[ch] = 0.f;
+                }
+            } else {
             const gp_u8 yrow = (gp_u8)P.data + (size_t)y * (size_t)P.step + (size_t)x0 * SB;
             uint32_t yw[SB], cw[SB];
             if constexpr (SD == SD_I420) {
@@ -322,6 +342,7 @@ __device__ __forceinline__ void pw4_body(const ChainArgs& c, const PlaneParams& 
 #pragma unroll
                 for (int ch = CN; ch < 4; ++ch) px[i].v[ch] = 0.f;
             }
+            } // 4:2:0
         } else {
 #pragma unroll
             for (int i = 0; i < 4; ++i)

@@ -107,6 +107,18 @@ class GpuMat:
         m.uv_offset = parent_uv + (y // 2 - y) * self.step
         return m
 
+    def yuv422_roi(self, x, y, w, h):
+        """Crop of a packed 4:2:2 surface (CV_8UC2: YUYV / UYVY): a plain view at an even x (a pixel-pair boundary); any y, any
+        width and height >= 1 (a view of odd width reads its whole last pair)."""
+        x, y, w, h = int(x), int(y), int(w), int(h)
+        if self.cv_type != make_type(DEPTH_8U, 2):
+            raise ValueError("packed 4:2:2 surfaces are CV_8UC2")
+        if x & 1:
+            raise ValueError("crops of packed 4:2:2 surfaces need an even x")
+        if x < 0 or y < 0 or w < 1 or h < 1 or x + w > self.cols or y + h > self.rows:
+            raise ValueError("ROI outside the matrix")
+        return GpuMat(h, w, self.cv_type, self.data + y * self.step + 2 * x, self.step, owner=self.owner)
+
 
 def _scalar(vals, n=4):
     vals = list(vals) if hasattr(vals, "__len__") else [vals]
@@ -249,13 +261,25 @@ def read_nv12(mat, dsize=None, color_range=capi.YUV_FULL, primaries=capi.BT709, 
     """fk::ReadYUV<NV12> + fk::ConvertYUVToRGB<NV12, range, primaries, alpha, floatN>, optionally as the
     BackIOp of fk::Resize<INTER_LINEAR> (reference tests/resize/test_fused_resize.cu:141-143).
     `mat` is the CV_8UC1 luma view (rows = luma height); the UV plane follows it in memory.  layout = YUV_P010: the luma
-    view is CV_16UC1 (10-bit codes in the high bits of 16-bit samples) and R, G, B come out on the 0..1023 scale."""
+    view is CV_16UC1 (10-bit codes in the high bits of 16-bit samples) and R, G, B come out on the 0..1023 scale.
+    layout = YUV_YUYV / YUV_UYVY: `mat` is a packed 4:2:2 surface, CV_8UC2 (crops: GpuMat.yuv422_roi)."""
     kind = capi.READ_NV12 if dsize is None else capi.READ_NV12_RESIZE_LINEAR
     mats = [mat] if isinstance(mat, GpuMat) else list(mat)  # a list = N crops (GpuMat.nv12_roi) of decoder surfaces, one launch
-    rd = ReadIOp(kind, make_type(DEPTH_16U if layout == capi.YUV_P010 else DEPTH_8U, 1), mats, len(mats), dsize, IGNORE_AR, None,
-                 (color_range, primaries, 1 if alpha else 0))
-    rd.yuv_layout = layout  # fk::ReadYUV<PF>: NV12 (the reference's), NV21, I420, YV12, P010
+    if layout in (capi.YUV_YUYV, capi.YUV_UYVY):
+        src_type = make_type(DEPTH_8U, 2)
+    else:
+        src_type = make_type(DEPTH_16U if layout == capi.YUV_P010 else DEPTH_8U, 1)
+    rd = ReadIOp(kind, src_type, mats, len(mats), dsize, IGNORE_AR, None, (color_range, primaries, 1 if alpha else 0))
+    rd.yuv_layout = layout  # fk::ReadYUV<PF>: NV12 (the reference's), NV21, I420, YV12, P010; packed 4:2:2: YUYV, UYVY
     return rd
+
+
+def read_yuv422(mat, dsize=None, color_range=capi.YUV_FULL, primaries=capi.BT709, alpha=True, layout=capi.YUV_YUYV):
+    """read_nv12 for packed 4:2:2 surfaces (capture cards, V4L2 cameras, 4:2:2 JPEG decoders): `mat` is CV_8UC2, layout YUV_YUYV
+    (bytes Y0 U Y1 V per pixel pair) or YUV_UYVY (U Y0 V Y1)."""
+    if layout not in (capi.YUV_YUYV, capi.YUV_UYVY):
+        raise ValueError("read_yuv422 takes layout YUV_YUYV or YUV_UYVY")
+    return read_nv12(mat, dsize, color_range, primaries, alpha, layout)
 
 
 def convertTo(in_type, out_type, alpha=None, beta=None):

@@ -227,6 +227,54 @@ inline auto cvtColorP010(const cv::cuda::GpuMat& p010, const std::array<cv::Rect
     internal::yuv_surface_crops(rd, p010, crops);
     return rd;
 }
+// cvtColorYUY2<cv::COLOR_YUV2RGB_YUY2 | BGR | RGBA | BGRA[, range, primaries]>(surf[, crops]) and cvtColorUYVY<cv::COLOR_YUV2*_UYVY ...>:
+// the same IOp for packed 4:2:2 surfaces of cameras, capture cards and 4:2:2 JPEG decoders (CV_8UC2 GpuMat, rows = H; bytes Y0 U Y1 V /
+// U Y0 V Y1 per pixel pair).  Crops are plain views at an even x (any y, width, height).
+namespace internal {
+template <fk::PixelFormat PF, cv::ColorConversionCodes RGB, cv::ColorConversionCodes BGR, cv::ColorConversionCodes RGBA, cv::ColorConversionCodes BGRA,
+          cv::ColorConversionCodes CODE, fk::ColorRange CR, fk::ColorPrimitives CP>
+inline auto yuv422_surface_read(const cv::cuda::GpuMat& surf, const char* what) {
+    static_assert(CODE == RGB || CODE == BGR || CODE == RGBA || CODE == BGRA, "Color conversion type not supported yet.");
+    if (surf.type() != CV_8UC2) throw std::runtime_error(std::string(what) + " needs a packed 4:2:2 surface (CV_8UC2)");
+    constexpr bool alpha = CODE == RGBA || CODE == BGRA;
+    constexpr bool swap = CODE == BGR || CODE == BGRA;
+    using O = std::conditional_t<alpha, float4, float3>;
+    fk::RawPtr<fk::_2D, uchar> view;
+    view.data = (uchar*)surf.data;
+    view.dims = {(uint)surf.cols, (uint)surf.rows, (uint)surf.step};
+    return fk::YuvRead<PF, CR, CP, alpha, O, swap>{view};
+}
+template <typename Read, size_t N>
+inline void yuv422_surface_crops(Read& rd, const cv::cuda::GpuMat& surf, const std::array<cv::Rect, N>& crops) {
+    const int step = (int)surf.step;
+    for (const cv::Rect& r : crops) {
+        if (r.x & 1) throw std::runtime_error("crops of packed 4:2:2 surfaces need an even x");
+        if (r.x < 0 || r.y < 0 || r.width < 1 || r.height < 1 || r.x + r.width > surf.cols || r.y + r.height > surf.rows)
+            throw std::runtime_error("packed 4:2:2 crop outside the surface");
+        rd.crops.push_back(cvgs_image2d{surf.data + (size_t)r.y * step + (size_t)r.x * 2, r.width, r.height, step, 0});
+    }
+}
+} // namespace internal
+template <cv::ColorConversionCodes CODE, fk::ColorRange CR = fk::Full, fk::ColorPrimitives CP = fk::bt709>
+inline auto cvtColorYUY2(const cv::cuda::GpuMat& surf) {
+    return internal::yuv422_surface_read<fk::YUYV, cv::COLOR_YUV2RGB_YUY2, cv::COLOR_YUV2BGR_YUY2, cv::COLOR_YUV2RGBA_YUY2, cv::COLOR_YUV2BGRA_YUY2, CODE, CR, CP>(surf, "cvtColorYUY2");
+}
+template <cv::ColorConversionCodes CODE, fk::ColorRange CR = fk::Full, fk::ColorPrimitives CP = fk::bt709, size_t N>
+inline auto cvtColorYUY2(const cv::cuda::GpuMat& surf, const std::array<cv::Rect, N>& crops) {
+    auto rd = cvtColorYUY2<CODE, CR, CP>(surf);
+    internal::yuv422_surface_crops(rd, surf, crops);
+    return rd;
+}
+template <cv::ColorConversionCodes CODE, fk::ColorRange CR = fk::Full, fk::ColorPrimitives CP = fk::bt709>
+inline auto cvtColorUYVY(const cv::cuda::GpuMat& surf) {
+    return internal::yuv422_surface_read<fk::UYVY, cv::COLOR_YUV2RGB_UYVY, cv::COLOR_YUV2BGR_UYVY, cv::COLOR_YUV2RGBA_UYVY, cv::COLOR_YUV2BGRA_UYVY, CODE, CR, CP>(surf, "cvtColorUYVY");
+}
+template <cv::ColorConversionCodes CODE, fk::ColorRange CR = fk::Full, fk::ColorPrimitives CP = fk::bt709, size_t N>
+inline auto cvtColorUYVY(const cv::cuda::GpuMat& surf, const std::array<cv::Rect, N>& crops) {
+    auto rd = cvtColorUYVY<CODE, CR, CP>(surf);
+    internal::yuv422_surface_crops(rd, surf, crops);
+    return rd;
+}
 template <int INTER_F, fk::PixelFormat PF, fk::ColorRange CR, fk::ColorPrimitives CP, bool ALPHA, typename O, bool SW>
 inline auto resize(const fk::YuvRead<PF, CR, CP, ALPHA, O, SW>& nv12Read, const cv::Size& dsize) {
     static_assert(isSupportedInterpolation<INTER_F>, "Interpolation type not supported yet.");

@@ -104,7 +104,7 @@ enum class CircularTensorOrder { NewestFirst = 0, OldestFirst = 1 };
 enum class ColorPlanes { Standard = 0, Transposed = 1 };
 // fk::PixelFormat: the reference's tests instantiate NV12 only; NV21 / I420 / YV12 / P010 (10-bit codes in 16-bit samples, the
 // result on the 0..1023 scale) are this engine's further 4:2:0 readers (numeric values = cvgs_yuv_layout)
-enum PixelFormat { NV12 = 0, NV21 = 1, I420 = 2, YV12 = 3, P010 = 4 };
+enum PixelFormat { NV12 = 0, NV21 = 1, I420 = 2, YV12 = 3, P010 = 4, YUYV = 5, UYVY = 6 }; // YUYV / UYVY: packed 4:2:2, CV_8UC2 surfaces (cvgs_yuv_layout)
 enum ColorRange { Full = 0, Limited = 1 };
 enum ColorPrimitives { bt601 = 0, bt709 = 1, bt2020 = 2 };
 template <PixelFormat PF> using YuvSample = std::conditional_t<PF == P010, unsigned short, unsigned char>;
@@ -565,7 +565,7 @@ template <PixelFormat PF, ColorRange CR, ColorPrimitives CP, bool ALPHA, typenam
     }
     void lower_read(ChainBuilder& b, int kind) const {
         cvgs_read_desc& r = b.d.read;
-        r.kind = kind; r.src_type = PF == P010 ? CV_16UC1 : CV_8UC1;
+        r.kind = kind; r.src_type = PF == P010 ? CV_16UC1 : ((PF == YUYV || PF == UYVY) ? CV_8UC2 : CV_8UC1);
         r.yuv_range = (int)CR; r.yuv_primaries = (int)CP; r.yuv_alpha = ALPHA ? 1 : 0;
         r.yuv_layout = (int)PF;
         if (crops.empty()) b.src.assign(1, image2d(params));

@@ -153,7 +153,21 @@ typedef enum cvgs_yuv_primaries { CVGS_BT601 = 0, CVGS_BT709 = 1, CVGS_BT2020 = 
  *         BYTES.  The conversion works on the 10-bit codes (chroma centre 512, limited range 64..940 / 64..960) and delivers
  *         R, G, B on the 10-bit scale, 0..1023 (alpha = 1023): convertTo CV_16U for a 10-bit image, or scale by 1/1023 in
  *         the chain for a network input.                                                                             */
-typedef enum cvgs_yuv_layout { CVGS_YUV_NV12 = 0, CVGS_YUV_NV21 = 1, CVGS_YUV_I420 = 2, CVGS_YUV_YV12 = 3, CVGS_YUV_P010 = 4 } cvgs_yuv_layout;
+/* Packed 4:2:2 layouts (capture cards, V4L2 cameras, 4:2:2 JPEG decoders), accepted by both NV12 read kinds:
+ *   YUYV: bytes Y0 U Y1 V per pixel pair (YUY2);  UYVY: bytes U Y0 V Y1 per pixel pair.
+ * src_type is CV_8UC2; width / height in pixels, step in bytes; ONE plane, so uv_offset must be 0, and a row is a sequence of
+ * 4-byte pixel pairs: data and step are multiples of 4 (CVGS_ERR_INVALID otherwise).  Width and height may be odd.
+ * Pixel (x, y) has luma Y[y][x] and the chroma of its pair, U[y][x >> 1], V[y][x >> 1] -- the nearest-sample rule of the 4:2:0
+ * layouts with full vertical chroma resolution; conversion (range, primaries, alpha, fp32 operation order) and the bilinear blend
+ * are those of the 4:2:0 layouts, unchanged.  A crop is a plain view at an even x: data = frame + y*step + 2*x, any y, any
+ * width >= 1, any height >= 1.  A view of odd width reads the whole last pair: the bytes a plane may read are
+ * [0, 4 * ceil(width / 2)) of each of its rows, and nothing outside them is read; cvgs_plane_table_hull and the independence
+ * check of cvgs_execute_many use that range.  Device plane tables: CVGS_ERR_UNSUPPORTED (a table carries no layout tag).  */
+typedef enum cvgs_yuv_layout {
+    CVGS_YUV_NV12 = 0, CVGS_YUV_NV21 = 1, CVGS_YUV_I420 = 2, CVGS_YUV_YV12 = 3, CVGS_YUV_P010 = 4,
+    CVGS_YUV_YUYV = 5, /* bytes Y0 U Y1 V per pixel pair (YUY2, V4L2 YUYV) */
+    CVGS_YUV_UYVY = 6  /* bytes U Y0 V Y1 per pixel pair                   */
+} cvgs_yuv_layout;
 
 #define CVGS_READ_FLAG_TABLE_ON_DEVICE 1u /* `src` is a device table made by cvgs_plane_table_build */
 /* Device tables in cvgs_execute_many (ABI 6): the caller VOUCHES that nothing this table's planes read lies inside the output of another

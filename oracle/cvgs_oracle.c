@@ -183,8 +183,9 @@ typedef struct yuv_coeffs {
 /* Coefficients written as the 6-decimal literals of the published derivation from the standards' luma weights
  * (BT.601 Kr 0.299 Kb 0.114, BT.709 Kr 0.2126 Kb 0.0722, BT.2020 non-constant luminance Kr 0.2627 Kb 0.0593):
  * R = Y' + 2(1-Kr) Cr, B = Y' + 2(1-Kb) Cb, G = Y' - 2Kb(1-Kb)/Kg Cb - 2Kr(1-Kr)/Kg Cr; limited range scales luma by
- * 255/219 and chroma by 255/224 on 8-bit codes, by 1023/876 and 1023/896 on 10-bit codes.  tests/test_independent_pins.py
- * re-derives every set in float64. */
+ * 255/219 and chroma by 255/224 on 8-bit codes, by 1023/876 and 1023/896 on 10-bit codes.  tests/f64_model.py (yuv_matrix)
+ * re-derives every set in float64; tests/test_independent_pins.py probes all eighteen against it and
+ * tests/test_model_vs_oracle.py holds every layout x range x primaries to it on whole pictures. */
 static yuv_coeffs yuv_matrix(int range, int primaries, int ten_bit) {
     static const float full[3][4] = {{1.402f, -0.344136f, -0.714136f, 1.772f},
                                      {1.5748f, -0.187324f, -0.468124f, 1.8556f},

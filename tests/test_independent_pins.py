@@ -15,8 +15,10 @@ import numpy as np
 import pytest
 
 from cvgpuspeedup_amd import capi, cvgs
+from tests import f64_model as F
+from tests.f64_model import exact_window  # noqa: F401  (the model owns the exact window; kept under this name for the tests below)
 
-STANDARDS = {capi.BT601: (0.299, 0.114), capi.BT709: (0.2126, 0.0722)}
+STANDARDS = {capi.BT601: (0.299, 0.114), capi.BT709: (0.2126, 0.0722)}  # (BT.2020 and the 10-bit sets: test_every_literal_set... below)
 
 
 def derived_matrix(range_, primaries):
@@ -74,25 +76,35 @@ def test_oracle_yuv_matrix_equals_the_derivation_from_kr_kb(oracle, range_, prim
     check_probe(out, range_, primaries, "oracle")
 
 
-def exact_window(sw, sh, dw, dh, ar):
-    """The aspect-ratio window in exact arithmetic: scale by height, fall back to width when it does not fit, extents
-    rounded half away from zero (RN_EVEN: then down to even), centred (LEFT: x = 0).  Returns (x1, y1, x2, y2, margin)
-    where margin = distance of the rounded quantity from the nearest .5 tie."""
-    def rnd(q):
-        return int(q + Fraction(1, 2)), abs((q - int(q)) - Fraction(1, 2))
-    tw, m = rnd(Fraction(dh * sw, sh))
-    th = dh
-    if ar == cvgs.PRESERVE_AR_RN_EVEN:
-        tw -= tw % 2
-    if tw > dw:
-        tw = dw
-        th, m = rnd(Fraction(dw * sh, sw))
-        if ar == cvgs.PRESERVE_AR_RN_EVEN:
-            th -= th % 2
-    tw, th = max(tw, 1), max(th, 1)
-    x1 = 0 if ar == cvgs.PRESERVE_AR_LEFT else (dw - tw) // 2
-    y1 = (dh - th) // 2
-    return x1, y1, x1 + tw - 1, y1 + th - 1, float(m)
+def _probe(oracle, range_, primaries, ten_bit):
+    """(ysub, yscale, rv, gu, gv, bu) as the oracle applies them: three chroma pairs that isolate the coefficients (nv12_probe_surface),
+    NV12 codes or P010 samples (10-bit codes in the high bits)."""
+    mid, ysub = (512, 64 if range_ == capi.YUV_LIMITED else 0) if ten_bit else (128, 16 if range_ == capi.YUV_LIMITED else 0)
+    s = np.zeros((3, 6), np.uint16)
+    s[0:2, 0:4], s[0:2, 4:6] = ysub, ysub + 1
+    s[2] = [mid, mid + 1, mid + 1, mid, mid, mid]
+    s = (s << 6) if ten_bit else s.astype(np.uint8)
+    t = cvgs.CV_16UC1 if ten_bit else cvgs.CV_8UC1
+    out = np.zeros((2, 6, 3), np.float32)
+    rd = cvgs.read_nv12(cvgs.GpuMat(2, 6, t, s.ctypes.data, s.strides[0], owner=s), None, range_, primaries, False,
+                        capi.YUV_P010 if ten_bit else capi.YUV_NV12)
+    oracle.execute(cvgs.lower([rd, cvgs.write(cvgs.CV_32FC3, cvgs.GpuMat.from_array(out, cvgs.CV_32FC3))]))
+    assert (out[1] == out[0]).all() and out[0, 0, 2] == 0.0 and out[0, 2, 0] == 0.0
+    return ysub, float(out[0, 4, 0]), float(out[0, 0, 0]), float(out[0, 2, 1]), float(out[0, 0, 1]), float(out[0, 2, 2])
+
+
+@pytest.mark.parametrize("ten_bit", [False, True])
+@pytest.mark.parametrize("range_", [capi.YUV_FULL, capi.YUV_LIMITED])
+@pytest.mark.parametrize("primaries", [capi.BT601, capi.BT709, capi.BT2020])
+def test_every_literal_set_equals_the_models_derivation(oracle, range_, primaries, ten_bit):
+    """All eighteen coefficient sets of oracle/cvgs_oracle.c (BT.601 / BT.709 / BT.2020, full / limited, 8-bit / 10-bit codes) against
+    the float64 derivation from Kr / Kb of tests/f64_model.yuv_matrix, to half a unit of the literals' sixth decimal (plus the fp32
+    narrowing of a value below 2.2)."""
+    want = F.yuv_matrix(range_, primaries, ten_bit)[:6]
+    got = _probe(oracle, range_, primaries, ten_bit)
+    assert got[0] == want[0]
+    for k in range(1, 6):
+        assert abs(got[k] - want[k]) <= 0.5e-6 + 2.0 ** -23, (k, got[k], want[k])
 
 
 @pytest.mark.parametrize("ar", [cvgs.PRESERVE_AR, cvgs.PRESERVE_AR_RN_EVEN, cvgs.PRESERVE_AR_LEFT])

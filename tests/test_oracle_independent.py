@@ -20,20 +20,14 @@ def oracle_resize(oracle, img, dst, ar=cvgs.IGNORE_AR, bg=None):
 
 
 def formula_f64(img, dst):
-    """out(x,y) = sum of 4 taps, src = dst * float32(1/(dst/src)), floor, +1 clamped, weights from unclamped x2/y2."""
+    """out(x,y) = sum of 4 taps, src = dst * float32(1/(dst/src)), floor, +1 clamped, weights from unclamped x2/y2: a thin caller of the
+    independent model (tests/f64_model.py); tests/test_model_vs_oracle.py holds the oracle to the model's derived bound over a grid."""
+    from tests import f64_model as F
     h, w, cn = img.shape
-    fx = float(np.float32(1.0 / (dst[0] / w)))
-    fy = float(np.float32(1.0 / (dst[1] / h)))
-    xs = np.arange(dst[0], dtype=np.float32) * np.float32(fx)
-    ys = np.arange(dst[1], dtype=np.float32) * np.float32(fy)
-    x1 = np.floor(xs).astype(int); y1 = np.floor(ys).astype(int)
-    x2r = np.minimum(x1 + 1, w - 1); y2r = np.minimum(y1 + 1, h - 1)
-    wx2 = (xs.astype(np.float64) - x1); wx1 = 1.0 - wx2
-    wy2 = (ys.astype(np.float64) - y1); wy1 = 1.0 - wy2
+    xs, ys = F.resize_coords(dst[0], w), F.resize_coords(dst[1], h)
     f = img.astype(np.float64)
-    out = (f[y1][:, x1] * (wy1[:, None] * wx1[None, :])[..., None] + f[y1][:, x2r] * (wy1[:, None] * wx2[None, :])[..., None] +
-           f[y2r][:, x1] * (wy2[:, None] * wx1[None, :])[..., None] + f[y2r][:, x2r] * (wy2[:, None] * wx2[None, :])[..., None])
-    return out.transpose(2, 0, 1), (xs, ys)
+    val = F.bilinear(lambda ty, tx: F.Val(f[ty, tx], 0.0, F.DEPTH_32F), xs[None, :], ys[:, None], w, h)
+    return val.v.transpose(2, 0, 1), (xs.astype(np.float32), ys.astype(np.float32))
 
 
 @pytest.mark.parametrize("shape,dst", [((120, 60), (64, 128)), ((97, 211), (64, 128)), ((300, 500), (64, 128)),

@@ -25,22 +25,15 @@ def get_perspective_transform(src, dst):
 
 
 def warp_f64(img, inv, dsize, perspective):
-    """Independent restatement in float64 (no shared code with the oracle): zero outside, bilinear inside with the
-    right/bottom taps clamped to the last column/row."""
-    h, w = img.shape[:2]
-    dw, dh = dsize
-    inv = np.asarray(inv, np.float32).astype(np.float64).reshape(3, 3)
-    ys, xs = np.mgrid[0:dh, 0:dw].astype(np.float64)
-    sx = inv[0, 0] * xs + inv[0, 1] * ys + inv[0, 2]
-    sy = inv[1, 0] * xs + inv[1, 1] * ys + inv[1, 2]
-    if perspective:
-        den = inv[2, 0] * xs + inv[2, 1] * ys + inv[2, 2]
-        sx, sy = sx / den, sy / den
-    inside = (sx >= 0) & (sx < w) & (sy >= 0) & (sy < h)
-    sxc, syc = np.where(inside, sx, 0.0), np.where(inside, sy, 0.0)
-    x1, y1 = np.floor(sxc).astype(np.int64), np.floor(syc).astype(np.int64)
-    x2r, y2r = np.minimum(x1 + 1, w - 1), np.minimum(y1 + 1, h - 1)
-    ax, ay = (sxc - x1)[..., None], (syc - y1)[..., None]
-    im = img.astype(np.float64).reshape(h, w, -1)
-    out = (im[y1, x1] * (1 - ax) * (1 - ay) + im[y1, x2r] * ax * (1 - ay) + im[y2r, x1] * (1 - ax) * ay + im[y2r, x2r] * ax * ay)
-    return np.where(inside[..., None], out, 0.0), inside, sx, sy
+    """The float64 restatement of the warp: a thin caller of the independent model (tests/f64_model.py: zero outside, bilinear inside with
+    the right/bottom taps clamped to the last column/row, coordinates in float64 from the fp32-narrowed inverse matrix).
+    Returns (values [y][x][c], inside, sx, sy)."""
+    from types import SimpleNamespace
+
+    from tests import f64_model as F
+    img = np.asarray(img)
+    cn = 1 if img.ndim == 2 else img.shape[2]
+    depth = {np.dtype(np.uint8): F.DEPTH_8U, np.dtype(np.uint16): F.DEPTH_16U, np.dtype(np.int16): F.DEPTH_16S, np.dtype(np.float32): F.DEPTH_32F}[img.dtype]
+    rd = SimpleNamespace(dsize=(int(dsize[0]), int(dsize[1])), src_type=depth + ((cn - 1) << 3))
+    val, _, (sx, sy, inside) = F._warp_plane(rd, F.View(img), list(np.asarray(inv, np.float64).reshape(-1)), bool(perspective), F.SPEC)
+    return val.v, inside, sx, sy

@@ -57,6 +57,7 @@ PRESERVE_AR, IGNORE_AR, PRESERVE_AR_RN_EVEN, PRESERVE_AR_LEFT = 0, 1, 2, 3
 YUV_FULL, YUV_LIMITED = 0, 1
 YUV_NV12, YUV_NV21, YUV_I420, YUV_YV12, YUV_P010 = 0, 1, 2, 3, 4
 YUV_YUYV, YUV_UYVY = 5, 6  # packed 4:2:2: bytes Y0 U Y1 V / U Y0 V Y1 per pixel pair (CV_8UC2 surfaces)
+YUV_I444 = 7  # planar 4:4:4: full-resolution planes Y, U, V, uv_offset bytes apart (CV_8UC1 luma view, uv_offset always stated)
 BT601, BT709, BT2020 = 0, 1, 2
 READ_FLAG_TABLE_ON_DEVICE = 1
 READ_FLAG_TABLE_SOURCES_VOUCHED = 2

@@ -70,6 +70,7 @@ bool is_resize(int kind) { return kind == CVGS_READ_RESIZE_LINEAR || kind == CVG
 constexpr int kMaxDim = CVGS_MAX_DIM; // widest / tallest plane the 32-bit index arithmetic of the kernels is specified for
 bool is_nv12(int kind) { return kind == CVGS_READ_NV12 || kind == CVGS_READ_NV12_RESIZE_LINEAR; }
 bool is_yuv422(int layout) { return layout == CVGS_YUV_YUYV || layout == CVGS_YUV_UYVY; } // packed 4:2:2: one plane of 4-byte pixel pairs
+bool is_yuv444(int layout) { return layout == CVGS_YUV_I444; } // planar 4:4:4: three full-resolution planes, uv_offset apart
 bool is_warp(int kind) { return kind == CVGS_READ_WARP_AFFINE || kind == CVGS_READ_WARP_PERSPECTIVE; }
 
 // Host half of fk::Resize::build: the kernel-side scale factors and the aspect-ratio window.
@@ -216,7 +217,7 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
     // CV_64F / CV_16F / CV_16BF sources: per-pixel reads and the bilinear resize (taps are cast to float, the output is CV_32F, reference
     // include/cvGPUSpeedup.cuh:227); CV_16F / CV_16BF also as a warp source.  A CV_64F warp source has no kernel.
     if (is_nv12(rd.kind)) {
-        if (rd.yuv_layout < CVGS_YUV_NV12 || rd.yuv_layout > CVGS_YUV_UYVY) return fail(CVGS_ERR_INVALID, "bad yuv_layout");
+        if (rd.yuv_layout < CVGS_YUV_NV12 || rd.yuv_layout > CVGS_YUV_I444) return fail(CVGS_ERR_INVALID, "bad yuv_layout");
         if (rd.yuv_range < CVGS_YUV_FULL || rd.yuv_range > CVGS_YUV_LIMITED) return fail(CVGS_ERR_INVALID, "bad yuv_range");
         if (rd.yuv_primaries < CVGS_BT601 || rd.yuv_primaries > CVGS_BT2020) return fail(CVGS_ERR_INVALID, "bad yuv_primaries");
         if (rd.yuv_layout == CVGS_YUV_P010) {
@@ -247,7 +248,7 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
     // layouts (2-byte alignment, even steps, whole surfaces: checked below for HOST descriptors only) cannot be checked on a
     // table this call cannot read -- a table built for NV12 and executed as I420 would address a second chroma plane that is not there
     if (table && is_nv12(rd.kind) && rd.yuv_layout != CVGS_YUV_NV12 && rd.yuv_layout != CVGS_YUV_NV21)
-        return fail(CVGS_ERR_UNSUPPORTED, "device plane tables serve the NV12 / NV21 layouts only (P010 / I420 / YV12 / YUYV / UYVY: host descriptors)");
+        return fail(CVGS_ERR_UNSUPPORTED, "device plane tables serve the NV12 / NV21 layouts only (P010 / I420 / YV12 / YUYV / UYVY / I444: host descriptors)");
 
     // ---- read stage ----
     ReadArgs& R = L.args.read;
@@ -313,7 +314,8 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
             const int esz = depth_bytes(sdepth) * scn;
             if (im.step < im.width * esz) return fail(CVGS_ERR_INVALID, "source step smaller than a row");
             const bool p422 = is_nv12(rd.kind) && is_yuv422(rd.yuv_layout);
-            if (is_nv12(rd.kind) && !p422 && ((im.width & 1) || (im.height & 1)))
+            const bool p444 = is_nv12(rd.kind) && is_yuv444(rd.yuv_layout);
+            if (is_nv12(rd.kind) && !p422 && !p444 && ((im.width & 1) || (im.height & 1)))
                 return fail(CVGS_ERR_INVALID, "NV12 planes need even dimensions");
             PlaneParams& P = L.planes[(size_t)z];
             P.data = (const uint8_t*)im.data;
@@ -325,6 +327,12 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
                 if (((uintptr_t)im.data | (uintptr_t)im.step) & 3) return fail(CVGS_ERR_INVALID, "YUYV / UYVY surfaces need data and step that are multiples of 4");
                 if ((int64_t)im.step < 4 * (((int64_t)im.width + 1) / 2)) return fail(CVGS_ERR_INVALID, "source step smaller than a row of whole pixel pairs");
                 P.uv_off = 0;
+            } else if (p444) { // three planes uv_offset apart, one step; any size, any alignment (the kernels assume none)
+                if (im.uv_offset == 0) return fail(CVGS_ERR_INVALID, "I444 surfaces state uv_offset (Y -> U = U -> V distance in bytes): 0 has no default meaning");
+                if (im.uv_offset < 0 || (int64_t)im.uv_offset < ((int64_t)im.height - 1) * im.step + im.width)
+                    return fail(CVGS_ERR_INVALID, "I444 uv_offset smaller than the view's plane: the planes would overlap");
+                if ((int64_t)im.uv_offset > ((int64_t)1 << 30)) return fail(CVGS_ERR_UNSUPPORTED, "I444 surfaces whose planes lie more than 2^30 bytes apart");
+                P.uv_off = (int32_t)im.uv_offset;
             } else if (is_nv12(rd.kind)) {
                 if (im.uv_offset < 0 || (im.uv_offset & 1)) return fail(CVGS_ERR_INVALID, "NV12 uv_offset must be even and non-negative");
                 if (rd.yuv_layout == CVGS_YUV_P010 && (((uintptr_t)im.data | (uintptr_t)im.step | (uintptr_t)im.uv_offset) & 1))
@@ -863,6 +871,21 @@ struct Upload {
     ~Upload() { done(false); }
 };
 
+// The resize kernel family of a decode-side chain: planar 4:4:4 has its own (k_yuv444.hip: any plane width); every other layout is
+// launch_nv12's business.  1 launched / 0 not eligible / < 0 error.
+int launch_yuv_resize(const ChainArgs& c, const PlaneParams* inline_planes, int n_inline, int min_width, LaunchCtx& ctx, bool dry_run, LaunchInfo* info,
+                      uint32_t chain_flags = 0) {
+    if (is_yuv444(c.read.yuv_layout)) return launch_yuv444(c, inline_planes, n_inline, ctx, dry_run, info);
+    return launch_nv12(c, inline_planes, n_inline, min_width, ctx, dry_run, info, chain_flags);
+}
+// stretch geometry on every plane, and rows the family's tap window fits into (K4, 4:2:2: k4_planes_eligible; 4:4:4: any width)
+bool yuv_planes_eligible(int layout, const PlaneParams* planes, int n, int dst_w, int dst_h) {
+    if (!is_yuv444(layout)) return k4_planes_eligible(planes, n, dst_w, dst_h);
+    for (int i = 0; i < n; ++i)
+        if (planes[i].x1 != 0 || planes[i].y1 != 0 || planes[i].x2 != dst_w - 1 || planes[i].y2 != dst_h - 1) return false;
+    return true;
+}
+
 int dispatch(const cvgs_chain_desc* ch, Lowered& L, hipStream_t stream, bool dry_run, LaunchInfo* info) {
     Upload up;
     const bool has_mirrors = L.mirrors.n > 0;
@@ -881,7 +904,7 @@ int dispatch(const cvgs_chain_desc* ch, Lowered& L, hipStream_t stream, bool dry
         if (!big_inline && !has_mirrors && is_nv12(L.args.read.kind)) { // K4: crops of a decoder surface into a planar tensor
             int min_w = 1 << 30;
             for (size_t i = 0; i < L.planes.size() && (int)i < L.args.read.used; ++i) min_w = L.planes[i].w < min_w ? L.planes[i].w : min_w;
-            big_inline = launch_nv12(L.args, L.planes.data(), (int)L.planes.size(), min_w, probe, true, nullptr) == 1;
+            big_inline = launch_yuv_resize(L.args, L.planes.data(), (int)L.planes.size(), min_w, probe, true, nullptr) == 1;
         }
     }
     const bool up_src = warp ? (int)L.warp_planes.size() > (L.uses_64f ? kInlineWarp64 : kInlineWarp)
@@ -952,17 +975,17 @@ int dispatch(const cvgs_chain_desc* ch, Lowered& L, hipStream_t stream, bool dry
             int min_w = 1 << 30; // over the planes that are read (default-value planes carry no source)
             for (int i = 0; i < n_inline && i < L.args.read.used; ++i) min_w = inline_planes[i].w < min_w ? inline_planes[i].w : min_w;
             if (up_src && is_nv12(L.args.read.kind) && L.args.read.used == L.args.read.batch &&
-                k4_planes_eligible(L.planes.data(), (int)L.planes.size(), L.args.read.dst_w, L.args.read.dst_h)) {
+                yuv_planes_eligible(L.args.read.yuv_layout, L.planes.data(), (int)L.planes.size(), L.args.read.dst_w, L.args.read.dst_h)) {
                 // more than 64 crops of a decoder surface: K4 reads the staged table as ONE segment of its fused-chain form
                 // (the planes are known on the host here, so its per-plane preconditions can be checked)
                 const ManySeg seg{L.args.read.table, L.args.write.data, L.args.read.batch, L.args.read.used};
                 LaunchCtx one(stream);
                 one.segs = &seg;
                 one.n_segs = 1;
-                rc = launch_nv12(L.args, nullptr, 0, 4, one, dry_run, info);
+                rc = launch_yuv_resize(L.args, nullptr, 0, 4, one, dry_run, info);
             } else {
                 LaunchCtx plain(stream);
-                rc = launch_nv12(L.args, inline_planes, n_inline, min_w, plain, dry_run, info, ch->flags);
+                rc = launch_yuv_resize(L.args, inline_planes, n_inline, min_w, plain, dry_run, info, ch->flags);
             }
             if (rc < 0) return fail(CVGS_ERR_HIP, "NV12 kernel launch failed");
             if (rc == 1) { up.done(true); return CVGS_OK; }
@@ -1035,6 +1058,10 @@ static void source_range(const cvgs_chain_desc& c, const cvgs_image2d& im, size_
     const bool p422 = yuv && is_yuv422(c.read.yuv_layout); // packed 4:2:2: whole 4-byte pixel pairs, no chroma plane
     const size_t last_row = p422 ? 4 * (((size_t)(im.width > 0 ? im.width : 1) + 1) / 2) : (size_t)(im.width > 0 ? im.width : 1) * px_bytes;
     const uint8_t* hi = lo + (size_t)im.step * (rows - 1) + last_row;
+    if (yuv && is_yuv444(c.read.yuv_layout)) { // planar 4:4:4: the view's rows again in the U and the V plane, uv_offset and 2 * uv_offset further
+        *out = ByteRange{lo, hi + 2 * (size_t)(im.uv_offset > 0 ? im.uv_offset : 0)};
+        return;
+    }
     if (yuv && !p422) {
         // 4:2:0 surfaces: the chroma rows are read too -- behind the luma rows (whole surfaces: height * 3 / 2 rows) or,
         // for a crop view, uv_offset bytes from its first luma byte (+ half the crop's rows).  Planar chroma (I420 / YV12: two
@@ -1170,7 +1197,7 @@ int execute_many(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream) {
                            CVGS_TYPE_DEPTH(chains[0].read.src_type) == CVGS_DEPTH_8U;
         const bool k4_il = chains[0].read.kind == CVGS_READ_NV12_RESIZE_LINEAR &&
                            (chains[0].read.yuv_layout == CVGS_YUV_NV12 || chains[0].read.yuv_layout == CVGS_YUV_NV21 || chains[0].read.yuv_layout == CVGS_YUV_P010 ||
-                            is_yuv422(chains[0].read.yuv_layout)); // interleaved chroma / packed 4:2:2
+                            is_yuv422(chains[0].read.yuv_layout) || is_yuv444(chains[0].read.yuv_layout)); // interleaved chroma / packed 4:2:2 / planar 4:4:4
         if (!tables0 && inline_ok && (k1_u8 || k4_il)) {
             size_t planes = 0;
             for (int i = 0; i < n; ++i) planes += (size_t)(chains[i].read.batch > 0 ? chains[i].read.batch : 0);
@@ -1209,7 +1236,7 @@ int execute_many(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream) {
             LaunchCtx pctx(stream);
             pctx.segs = &one;
             pctx.n_segs = 1;
-            if (k4) fusable = !tables && launch_nv12(probe, nullptr, 0, 1 << 30, pctx, true, nullptr) == 1; // K4 checks its planes on the host
+            if (k4) fusable = !tables && launch_yuv_resize(probe, nullptr, 0, 1 << 30, pctx, true, nullptr) == 1; // K4 checks its planes on the host
             else fusable = launch_k1(probe, nullptr, 0, pctx, true, nullptr) == 1;
         }
         // host descriptors: the table goes into a slot of the stream's own ring, recycled through the launch's progress word (ManyPool) --
@@ -1239,7 +1266,7 @@ int execute_many(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream) {
             if (i > 0) rc = lower(&chains[i], false, L);
             if (rc) return rc; // nothing enqueued yet
             if (k4 && (L.args.read.used != L.args.read.batch ||
-                       !k4_planes_eligible(L.planes.data(), (int)L.planes.size(), L.args.read.dst_w, L.args.read.dst_h))) {
+                       !yuv_planes_eligible(L.args.read.yuv_layout, L.planes.data(), (int)L.planes.size(), L.args.read.dst_w, L.args.read.dst_h))) {
                 fusable = false; // e.g. a 2-pixel-wide crop: the one-by-one path sends that chain to the interpreted kernel
                 break;
             }
@@ -1274,7 +1301,7 @@ int execute_many(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream) {
                 ctx.done_word = ms->done_dev;
                 ctx.done_value = ms->next_seq - 1;
             }
-            rc = k4 ? launch_nv12(c, inline_many ? inline_planes.data() : nullptr, inline_many ? (int)inline_planes.size() : 0, 1 << 30, ctx, false, nullptr)
+            rc = k4 ? launch_yuv_resize(c, inline_many ? inline_planes.data() : nullptr, inline_many ? (int)inline_planes.size() : 0, 1 << 30, ctx, false, nullptr)
                     : launch_k1(c, inline_many ? inline_planes.data() : nullptr, inline_many ? (int)inline_planes.size() : 0, ctx, false, nullptr);
             const bool reported = ctx.done_word_taken;
             if (rc != 1) return fail(CVGS_ERR_HIP, "fused kernel launch failed");
@@ -1766,7 +1793,7 @@ static int queue_submit_one(cvgs_queue_t h, const cvgs_chain_desc* chain, uint64
     Lowered L;
     int rc = lower(chain, false, L);
     if (rc) return rc;
-    if (L.uses_64f || L.int_arith || L.mirrors.n > 0 || is_warp(L.args.read.kind) || is_yuv422(L.args.read.yuv_layout) || (chain->flags & CVGS_CHAIN_FORCE_GENERIC))
+    if (L.uses_64f || L.int_arith || L.mirrors.n > 0 || is_warp(L.args.read.kind) || is_yuv422(L.args.read.yuv_layout) || is_yuv444(L.args.read.yuv_layout) || (chain->flags & CVGS_CHAIN_FORCE_GENERIC))
         return fail(CVGS_ERR_UNSUPPORTED, "queue: not a chain the server takes");
     std::string err;
     rc = cvgs::queue_submit(h->q, L.args, L.planes.data(), (int)L.planes.size(), ticket, err);
@@ -1804,7 +1831,7 @@ int cvgs_queue_submit_on(cvgs_queue_t h, const cvgs_chain_desc* chain, cvgs_stre
     const bool hybrid = (flags & CVGS_QUEUE_SUBMIT_HYBRID) != 0;
     std::string err;
     rc = 1;
-    if (!(L.uses_64f || L.int_arith || L.mirrors.n > 0 || is_warp(L.args.read.kind) || is_yuv422(L.args.read.yuv_layout) || (chain->flags & CVGS_CHAIN_FORCE_GENERIC))) {
+    if (!(L.uses_64f || L.int_arith || L.mirrors.n > 0 || is_warp(L.args.read.kind) || is_yuv422(L.args.read.yuv_layout) || is_yuv444(L.args.read.yuv_layout) || (chain->flags & CVGS_CHAIN_FORCE_GENERIC))) {
         const cvgs::ChainArgs* ca = &L.args;
         const cvgs::PlaneParams* pp = L.planes.data();
         const int np = (int)L.planes.size();
@@ -1847,7 +1874,7 @@ int cvgs_queue_submit_many_on(cvgs_queue_t h, const cvgs_chain_desc* const* chai
     for (int32_t i = 0; i < n; ++i) {
         if (int rc = lower(chains[i], false, L[(size_t)i])) return rc;
         const Lowered& l = L[(size_t)i];
-        servable = servable && !(l.uses_64f || l.int_arith || l.mirrors.n > 0 || is_warp(l.args.read.kind) || is_yuv422(l.args.read.yuv_layout) || (chains[i]->flags & CVGS_CHAIN_FORCE_GENERIC));
+        servable = servable && !(l.uses_64f || l.int_arith || l.mirrors.n > 0 || is_warp(l.args.read.kind) || is_yuv422(l.args.read.yuv_layout) || is_yuv444(l.args.read.yuv_layout) || (chains[i]->flags & CVGS_CHAIN_FORCE_GENERIC));
     }
     std::string err = "queue: not chains the server takes";
     int rc = 1, queued = 0;

@@ -227,6 +227,9 @@ bool k4_planes_eligible(const PlaneParams* planes, int n, int dst_w, int dst_h);
 // Packed 4:2:2 surfaces (YUYV / UYVY) read back inside the bilinear resize (k_yuv422.hip): K4's targets and dispatch rules; launch_nv12
 // forwards the two layouts here, so every caller of launch_nv12 serves them.  1 launched / 0 not eligible / < 0 error.
 int launch_yuv422(const ChainArgs& c, const PlaneParams* inline_planes, int n_inline, LaunchCtx& ctx, bool dry_run, LaunchInfo* info);
+// Planar 4:4:4 surfaces (I444) read back inside the bilinear resize (k_yuv444.hip): the same targets and rules -- both families run the
+// launcher of k_yuv_family.hpp.  launch_nv12 does not know the layout: cvgs_api.cpp sends such chains here.
+int launch_yuv444(const ChainArgs& c, const PlaneParams* inline_planes, int n_inline, LaunchCtx& ctx, bool dry_run, LaunchInfo* info);
 
 // Thread-fused pointwise chains on u8 sources (4 pixels per thread) -> fp32 planar / packed.
 // n_segs chains of ONE thread-fused pointwise shape (per-pixel reads of u8 planes -> fp32 tensor / packed fp32 pixels) in one launch: the

@@ -603,6 +603,11 @@ __device__ __forceinline__ void nv12_px(const PlaneParams& P, int x, int y, cons
         Y = (float)(yrow[x] >> 6);
         U = (float)(uv[0] >> 6);
         V = (float)(uv[1] >> 6);
+    } else if (k.layout == CVGS_YUV_I444) { // planar 4:4:4: full-resolution U and V planes uv_off and 2 * uv_off behind the luma plane
+        const uint8_t* py = P.data + (size_t)y * P.step + x;
+        Y = (float)py[0];
+        U = (float)py[(size_t)P.uv_off];
+        V = (float)py[2 * (size_t)P.uv_off];
     } else if (k.layout >= CVGS_YUV_YUYV) { // packed 4:2:2: Y0 U Y1 V (YUYV) or U Y0 V Y1 (UYVY) per pixel pair, chroma on every row
         const uint8_t* pr = P.data + (size_t)y * P.step + 4 * (size_t)(x >> 1);
         const int uy = k.layout == CVGS_YUV_UYVY ? 1 : 0;

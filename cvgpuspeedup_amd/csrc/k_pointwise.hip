@@ -248,6 +248,7 @@ hipError_t pw_launch_bf16(int prog_id, int sd, const ChainArgs& c, const PlanePa
                          : launch_pw<4, ArithProg<4, CVGS_DEPTH_32F>, __bf16, SD>(c, ip, ni, g, s);
     };
     if (sd == SD_YUV422) return go(std::integral_constant<int, SD_YUV422>{});
+    if (sd == SD_YUV444) return go(std::integral_constant<int, SD_YUV444>{});
     return sd == SD_P010 ? go(std::integral_constant<int, SD_P010>{})
                          : (sd == SD_I420 ? go(std::integral_constant<int, SD_I420>{}) : go(std::integral_constant<int, SD_NV12>{}));
 }
@@ -476,17 +477,19 @@ int launch_pointwise(const ChainArgs& c_in, const PlaneParams* inline_planes, in
         const bool ten = c.read.yuv_layout == CVGS_YUV_P010;
         const bool planar_chroma = c.read.yuv_layout == CVGS_YUV_I420 || c.read.yuv_layout == CVGS_YUV_YV12;
         const bool p422 = c.read.yuv_layout == CVGS_YUV_YUYV || c.read.yuv_layout == CVGS_YUV_UYVY; // packed 4:2:2: any width, x0 % 4 == 0 is a pair boundary
+        const bool p444 = c.read.yuv_layout == CVGS_YUV_I444; // planar 4:4:4: any width, any alignment
         if (info) {
-            static const char* names[4][3] = {{"pointwise4_nv12", "pointwise4_nv12_u8", "pointwise4_nv12_f16"},
+            static const char* names[5][3] = {{"pointwise4_nv12", "pointwise4_nv12_u8", "pointwise4_nv12_f16"},
                                               {"pointwise4_p010", "pointwise4_p010_u8", "pointwise4_p010_f16"},
                                               {"pointwise4_i420", "pointwise4_i420_u8", "pointwise4_i420_f16"},
-                                              {"pointwise4_yuv422", "pointwise4_yuv422_u8", "pointwise4_yuv422_f16"}};
-            info->kernel = names[p422 ? 3 : (ten ? 1 : (planar_chroma ? 2 : 0))][u8o ? 1 : (f16 ? 2 : 0)];
+                                              {"pointwise4_yuv422", "pointwise4_yuv422_u8", "pointwise4_yuv422_f16"},
+                                              {"pointwise4_yuv444", "pointwise4_yuv444_u8", "pointwise4_yuv444_f16"}};
+            info->kernel = names[p444 ? 4 : p422 ? 3 : (ten ? 1 : (planar_chroma ? 2 : 0))][u8o ? 1 : (f16 ? 2 : 0)];
             if (bf16) info->kernel = bf16_kernel_name(info->kernel);
         }
         if (dry_run) return 1;
         if (bf16) {
-            const hipError_t e = pw_launch_bf16(prog_id, p422 ? SD_YUV422 : (ten ? SD_P010 : (planar_chroma ? SD_I420 : SD_NV12)), c, inline_planes, n_inline, g, (hipStream_t)stream);
+            const hipError_t e = pw_launch_bf16(prog_id, p444 ? SD_YUV444 : p422 ? SD_YUV422 : (ten ? SD_P010 : (planar_chroma ? SD_I420 : SD_NV12)), c, inline_planes, n_inline, g, (hipStream_t)stream);
             return e == hipSuccess ? 1 : -(int)e - 1000;
         }
         const ProgArgs& p = c.prog;
@@ -502,7 +505,8 @@ int launch_pointwise(const ChainArgs& c_in, const PlaneParams* inline_planes, in
                         : launch_pw<CN, Arith, float, SD>(c, inline_planes, n_inline, g, s);
         };
         auto go_cn = [&](auto sd_tag) { return g.cn == 3 ? go(std::integral_constant<int, 3>{}, sd_tag) : go(std::integral_constant<int, 4>{}, sd_tag); };
-        e = p422 ? go_cn(std::integral_constant<int, SD_YUV422>{})
+        e = p444 ? go_cn(std::integral_constant<int, SD_YUV444>{})
+            : p422 ? go_cn(std::integral_constant<int, SD_YUV422>{})
             : ten ? go_cn(std::integral_constant<int, SD_P010>{})
                 : (planar_chroma ? go_cn(std::integral_constant<int, SD_I420>{}) : go_cn(std::integral_constant<int, SD_NV12>{}));
         return e == hipSuccess ? 1 : -(int)e - 1000;

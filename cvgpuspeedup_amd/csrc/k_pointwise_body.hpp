@@ -162,7 +162,8 @@ __device__ __forceinline__ float elem_value(const uint32_t* raw, int e) {
 // NV21 8-bit samples, P010 16-bit samples) -- the pixel arrives as CV_32F R, G, B[, A] through k_common.hpp's yuv_to_rgb
 constexpr int SD_NV12 = 64, SD_P010 = 65, SD_I420 = 66; // SD_I420: planar chroma (I420 / YV12: two quarter-size planes behind the luma)
 constexpr int SD_YUV422 = 67; // packed 4:2:2 (YUYV / UYVY): one plane of 4-byte pixel pairs, chroma on every row
-template <int SD> constexpr bool is_yuv_sd = SD == SD_NV12 || SD == SD_P010 || SD == SD_I420 || SD == SD_YUV422;
+constexpr int SD_YUV444 = 68; // planar 4:4:4 (I444): three full-resolution planes uv_off apart, no alignment
+template <int SD> constexpr bool is_yuv_sd = SD == SD_NV12 || SD == SD_P010 || SD == SD_I420 || SD == SD_YUV422 || SD == SD_YUV444;
 template <int SD> constexpr int src_elem_bytes = (SD == CVGS_DEPTH_8U || SD == CVGS_DEPTH_8S) ? 1 : ((SD == CVGS_DEPTH_16U || SD == CVGS_DEPTH_16S) ? 2 : 4);
 
 // The thread's 4 work pixels travel to the write stage BY VALUE.  Round 2 passed `const Px (&)[4]`: after inlining, LLVM kept
@@ -278,6 +279,32 @@ __device__ __forceinline__ void pw4_body(const ChainArgs& c, const PlaneParams& 
                 for (int i = 0; i < 4; ++i) {
                     const uint32_t w = q[i >> 1];
                     yuv_to_rgb((float)((w >> (16 * (i & 1))) & 0xffu), (float)((w >> 8) & 0xffu), (float)(w >> 24), yk, px[i]);
+#pragma unroll
+                    for (int ch = CN; ch < 4; ++ch) px[i].v[ch] = 0.f;
+                }
+            } else if constexpr (SD == SD_YUV444) {
+                // planar 4:4:4: the thread's 4 pixels are 4 bytes at x0 of the row in each of the three planes (any alignment); the pixels
+                // of a ragged tail are loaded singly -- nothing behind byte width - 1 of a row is read
+                const gp_u8 yrow = (gp_u8)P.data + (size_t)y * (size_t)P.step + (size_t)x0;
+                const gp_u8 urow = yrow + (size_t)P.uv_off, vrow = urow + (size_t)P.uv_off;
+                uint32_t q[3];
+                if (npx == 4) {
+                    q[0] = *(gp_u32)yrow;
+                    q[1] = *(gp_u32)urow;
+                    q[2] = *(gp_u32)vrow;
+                } else {
+                    q[0] = q[1] = q[2] = 0u;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k)
+                        if (k < npx) {
+                            q[0] |= (uint32_t)yrow[k] << (8 * k);
+                            q[1] |= (uint32_t)urow[k] << (8 * k);
+                            q[2] |= (uint32_t)vrow[k] << (8 * k);
+                        }
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    yuv_to_rgb((float)((q[0] >> (8 * i)) & 0xffu), (float)((q[1] >> (8 * i)) & 0xffu), (float)((q[2] >> (8 * i)) & 0xffu), yk, px[i]);
 #pragma unroll
                     for (int ch = CN; ch < 4; ++ch) px[i].v[ch] = 0.f;
                 }

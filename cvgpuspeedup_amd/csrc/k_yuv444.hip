@@ -1,34 +1,30 @@
-// k_yuv422.hip -- packed 4:2:2 surfaces (YUYV / UYVY: capture cards, V4L2 cameras, 4:2:2 JPEG decoders) read back inside the bilinear
-// resize: each of the 4 taps is converted YCbCr -> RGB(A) in float (k_common.hpp: k4_tap, the 4:2:0 kernels' conversion), THEN
-// interpolated, pushed through the pointwise program and written -- planar fp32 / fp16 / bf16 tensor, packed fp32 / fp16 pixels, packed
-// u8 image: the targets K4 (k_nv12.hip) serves for NV12, with K4's dispatch rules.
+// k_yuv444.hip -- planar 4:4:4 surfaces (I444: rocDecode's YUV444 output of 4:4:4 HEVC / AV1 streams, rocJPEG's output for non-subsampled
+// JPEGs) read back inside the bilinear resize: each of the 4 taps is converted YCbCr -> RGB(A) in float (k_common.hpp: k4_tap, the 4:2:0
+// kernels' conversion), THEN interpolated, pushed through the pointwise program and written -- planar fp32 / fp16 / bf16 tensor, packed
+// fp32 / fp16 pixels, packed u8 image: the targets K4 (k_nv12.hip) and k_yuv422_resize serve, with their dispatch rules (the shared
+// launcher of k_yuv_family.hpp).
 //
 // Mapping (as K1 / K4): lane = output column, wave = RPW output rows of one plane, blockIdx.y / .z = row group / plane (fused chains:
-// plane / chain).  A row of the surface is a sequence of 4-byte pixel pairs {Y0 U Y1 V} (UYVY: {U Y0 V Y1}); the taps x1 and x1 + 1 lie
-// in pair m = x1 >> 1 and at most m + 1, so ONE 8-byte load at 4 * m -- clamped back into the row when m is the last pair; rows of a
-// single pair: one 4-byte load -- brings both lumas and both chroma pairs of a source row: two loads per output pixel, 4-byte aligned,
-// where K4 needs four.  The twelve samples are picked out of the two windows with v_perm_b32; the byte order is a wave-uniform XOR on
-// the selectors, not a second set of kernels.  The bytes a plane reads are [0, 4 * ceil(w / 2)) of each of its rows, nothing else.
+// plane / chain).  The surface is three full-resolution planes Y, U, V that share one step and lie uv_off bytes apart; the taps x1 and
+// x1 + 1 of a source row of a plane arrive in ONE 2-byte load at column x1 -- clamped back into the row when x1 is the last column; rows
+// of width 1: one byte load -- so an output pixel costs six loads (3 planes x 2 rows), all issued before the first is used.  Nothing is
+// assumed about the alignment of data, step or uv_off; row bases are wave-uniform, lane offsets 32-bit, and the three plane bases are
+// computed once per wave on the scalar side.  The bytes a plane reads are [0, w) of each of its h rows in each of the three planes.
 #include "k_yuv_family.hpp"
 
 namespace cvgs {
 
-typedef uint32_t y422_u32x2 __attribute__((ext_vector_type(2)));
-typedef y422_u32x2 y422_u32x2_a4 __attribute__((aligned(4)));
-typedef const __attribute__((address_space(1))) y422_u32x2_a4* gptr_pair2; // two pixel pairs
-typedef const __attribute__((address_space(1))) uint32_t* gptr_pair1;      // one pixel pair
+typedef uint16_t y444_u16u __attribute__((aligned(1)));
+typedef const __attribute__((address_space(1))) y444_u16u* gptr_tap2; // both horizontal taps of one source row of one plane
 
-// the geometry block, the argument-block forms (NPL > 0 / == 0 / < 0) and the launcher are the YUV families' common ones (k_yuv_family.hpp)
-struct Y422Geom : YuvFamGeom {};
-template <int NPL> using Y422Args = YuvFamArgs<NPL>;
-constexpr int kY422Waves = kYuvFamWaves;
-constexpr int kY422TileRow = kYuvFamTileRow;
+constexpr int kY444Waves = kYuvFamWaves;
+constexpr int kY444TileRow = kYuvFamTileRow;
 
 // RPW output rows per wave; CN output channels (3, or 4 with alpha).  WIN: the target may hold an aspect-ratio window and default-value
 // planes (usedPlanes < BATCH) -- K1's / K4's machinery: the background value runs through the program once, pixels outside the window
 // take it; a separate instantiation, so that stretch-only launches do not pay for the selects.
 template <int NPL, class Prog, typename OT = float, int RPW = 1, int CN = 3, bool WIN = false>
-__global__ __launch_bounds__(64 * kY422Waves) void k_yuv422_resize(const Y422Args<NPL> a, const Y422Geom g) {
+__global__ __launch_bounds__(64 * kY444Waves) void k_yuv444_resize(const YuvFamArgs<NPL> a, const YuvFamGeom g) {
     const ChainArgs& c = a.c;
     const int dst_w = g.dst_w, dst_h = g.dst_h, W = g.out_w;
     PlaneParams P;
@@ -57,15 +53,14 @@ __global__ __launch_bounds__(64 * kY422Waves) void k_yuv422_resize(const Y422Arg
         row_group = (int)blockIdx.y;
     }
     const int yuv_range = c.read.yuv_range, yuv_prim = c.read.yuv_primaries, packed = g.packed;
-    const uint32_t uyvy = c.read.yuv_layout == CVGS_YUV_UYVY ? 1u : 0u; // wave-uniform: every sample sits at its YUYV byte ^ 1
     const int64_t img_stride = g.img_stride, ch_stride = g.ch_stride;
     typedef float f32x4s __attribute__((ext_vector_type(4)));
     const f32x4s op0 = *(const f32x4s*)c.prog.operand[0], op1 = *(const f32x4s*)c.prog.operand[1],
                  op2 = *(const f32x4s*)c.prog.operand[2], op3 = *(const f32x4s*)c.prog.operand[3];
     // one batch of scalar loads, one wait, in front of the first branch (see k_k1.hip)
     if constexpr (WIN) asm volatile("" ::"s"(used), "s"(P.x1), "s"(P.y1), "s"(P.x2), "s"(P.y2));
-    asm volatile("" ::"s"(dst_w), "s"(dst_h), "s"(W), "s"(CN), "s"(P.w), "s"(P.h), "s"(P.step), "s"(P.fx), "s"(P.fy), "s"(P.data),
-                 "s"(yuv_range), "s"(yuv_prim), "s"(uyvy), "s"(packed), "s"(img_stride), "s"(ch_stride), "s"(out_base), "s"(op0), "s"(op1),
+    asm volatile("" ::"s"(dst_w), "s"(dst_h), "s"(W), "s"(CN), "s"(P.w), "s"(P.h), "s"(P.step), "s"(P.fx), "s"(P.fy), "s"(P.data), "s"(P.uv_off),
+                 "s"(yuv_range), "s"(yuv_prim), "s"(packed), "s"(img_stride), "s"(ch_stride), "s"(out_base), "s"(op0), "s"(op1),
                  "s"(op2), "s"(op3));
     // (behind the scalar loads: a store in front of them would make the compiler fetch the descriptors with vector loads)
     if constexpr (NPL == 0) {
@@ -77,7 +72,7 @@ __global__ __launch_bounds__(64 * kY422Waves) void k_yuv422_resize(const Y422Arg
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = (int)(threadIdx.x & 63);
     const int x = col_tile * 64 + lane;
-    const int row0 = (row_group * kY422Waves + wave) * RPW;
+    const int row0 = (row_group * kY444Waves + wave) * RPW;
     if (row0 >= dst_h || x >= dst_w) return;
 
     // one output pixel of row y (wave-uniform row pointers; planar: non-temporal rows, packed: one store per pixel / a coalesced u8 tile)
@@ -153,20 +148,18 @@ __global__ __launch_bounds__(64 * kY422Waves) void k_yuv422_resize(const Y422Arg
     const int x2 = x1 + 1;
     const float wxa = (float)x2 - sx, wxb = sx - (float)x1;
     const int xa = max(0, min(x1, P.w - 1)), xb2 = max(xa, min(x2, P.w - 1)); // taps 0 / 1 (tap 1 repeats tap 0 at the right edge)
-    const int npairs = (P.w + 1) >> 1; // wave-uniform; >= 1
-    const bool single = npairs < 2;    // rows of one pixel pair: a 4-byte window
-    const int m0 = xa >> 1, m1 = xb2 >> 1;
-    const int wp = single ? 0 : min(m0, npairs - 2); // first pair of the 8-byte window: clamped back into the row at the last pair
-    const uint32_t wo = (uint32_t)wp * 4u;
-    // v_perm_b32 selectors into the window's 8 bytes (YUYV: luma at 4 * pair + 2 * (x & 1), U at 4 * pair + 1, V at 4 * pair + 3; UYVY: ^ 1):
-    //   sel_yu -> {Y tap 0, Y tap 1, U tap 0, U tap 1},  sel_v -> {V tap 0, V tap 1, 0, 0}
-    const uint32_t b0 = (uint32_t)(m0 - wp) * 4u, b1 = (uint32_t)(m1 - wp) * 4u;
-    const uint32_t sel_yu = ((b0 + 2u * (uint32_t)(xa & 1)) | ((b1 + 2u * (uint32_t)(xb2 & 1)) << 8) | ((b0 + 1u) << 16) | ((b1 + 1u) << 24)) ^ (uyvy * 0x01010101u);
-    const uint32_t sel_v = (((b0 + 3u) | ((b1 + 3u) << 8)) ^ (uyvy * 0x00000101u)) | 0x0c0c0000u;
-    const gptr_u8 base = (gptr_u8)P.data;
+    // both taps of a source row of a plane lie in ONE 2-byte window at xa -- clamped back into the row when xa is the last column; rows of
+    // a single pixel: a 1-byte window.  s0 / s1: the bit position of tap 0 / 1 inside the window.  Nothing is assumed about alignment.
+    const bool single = P.w < 2; // wave-uniform
+    const int xo = single ? 0 : min(xa, P.w - 2);
+    const uint32_t wo = (uint32_t)xo; // 32-bit lane offset
+    const uint32_t s0 = (uint32_t)(xa - xo) * 8u, s1 = (uint32_t)(xb2 - xo) * 8u;
+    // the three plane bases, once per wave on the scalar side: U and V lie uv_off and 2 * uv_off behind Y, all with the same step
+    const gptr_u8 ybase = (gptr_u8)P.data;
+    const gptr_u8 ubase = pin_uniform(ybase + (size_t)(uint32_t)P.uv_off), vbase = pin_uniform(ubase + (size_t)(uint32_t)P.uv_off);
     const size_t step = (size_t)P.step;
 
-    uint32_t wa_lo[RPW], wa_hi[RPW], wb_lo[RPW], wb_hi[RPW]; // the windows of source rows y1 / y2
+    uint32_t wy[RPW][2], wu[RPW][2], wv[RPW][2]; // the windows of source rows y1 / y2 in the three planes: six loads per output pixel
     float wya[RPW], wyb[RPW];
     bool in_y[RPW];
     // four rows per wave into a planar fp32 tensor: a full 64-column tile with all four rows inside the target leaves through the LDS transpose
@@ -185,15 +178,18 @@ __global__ __launch_bounds__(64 * kY422Waves) void k_yuv422_resize(const Y422Arg
         wya[j] = (float)y2 - sy;
         wyb[j] = sy - (float)y1;
         const int r1 = __builtin_amdgcn_readfirstlane(max(0, min(y1, P.h - 1))), r2 = __builtin_amdgcn_readfirstlane(max(0, min(y2, P.h - 1)));
-        const gptr_u8 ra = pin_uniform(base + (size_t)r1 * step);
-        const gptr_u8 rb = pin_uniform(base + (size_t)r2 * step);
+        const size_t o1 = (size_t)r1 * step, o2 = (size_t)r2 * step; // wave-uniform row offsets, shared by the planes
+        const gptr_u8 ya = pin_uniform(ybase + o1), yb = pin_uniform(ybase + o2);
+        const gptr_u8 ua = pin_uniform(ubase + o1), ub = pin_uniform(ubase + o2);
+        const gptr_u8 va = pin_uniform(vbase + o1), vb = pin_uniform(vbase + o2);
         if (single) { // wave-uniform
-            wa_lo[j] = wa_hi[j] = *(gptr_pair1)(ra + wo);
-            wb_lo[j] = wb_hi[j] = *(gptr_pair1)(rb + wo);
+            wy[j][0] = *(ya + wo); wy[j][1] = *(yb + wo);
+            wu[j][0] = *(ua + wo); wu[j][1] = *(ub + wo);
+            wv[j][0] = *(va + wo); wv[j][1] = *(vb + wo);
         } else {
-            const y422_u32x2 qa = *(gptr_pair2)(ra + wo), qb = *(gptr_pair2)(rb + wo);
-            wa_lo[j] = qa.x; wa_hi[j] = qa.y;
-            wb_lo[j] = qb.x; wb_hi[j] = qb.y;
+            wy[j][0] = *(gptr_tap2)(ya + wo); wy[j][1] = *(gptr_tap2)(yb + wo);
+            wu[j][0] = *(gptr_tap2)(ua + wo); wu[j][1] = *(gptr_tap2)(ub + wo);
+            wv[j][0] = *(gptr_tap2)(va + wo); wv[j][1] = *(gptr_tap2)(vb + wo);
         }
     }
 
@@ -201,14 +197,13 @@ __global__ __launch_bounds__(64 * kY422Waves) void k_yuv422_resize(const Y422Arg
     for (int j = 0; j < RPW; ++j) {
         const int y = row0 + j;
         if (y >= dst_h) break; // wave-uniform
-        // {Y0, Y1, U0, U1} and {V0, V1} of row a / row b
-        const uint32_t ayu = __builtin_amdgcn_perm(wa_hi[j], wa_lo[j], sel_yu), av = __builtin_amdgcn_perm(wa_hi[j], wa_lo[j], sel_v);
-        const uint32_t byu = __builtin_amdgcn_perm(wb_hi[j], wb_lo[j], sel_yu), bv = __builtin_amdgcn_perm(wb_hi[j], wb_lo[j], sel_v);
         float fy[4], fu[4], fv[4]; // taps 00, 10, 01, 11
-        fy[0] = (float)(ayu & 0xffu); fy[1] = (float)((ayu >> 8) & 0xffu); fu[0] = (float)((ayu >> 16) & 0xffu); fu[1] = (float)(ayu >> 24);
-        fy[2] = (float)(byu & 0xffu); fy[3] = (float)((byu >> 8) & 0xffu); fu[2] = (float)((byu >> 16) & 0xffu); fu[3] = (float)(byu >> 24);
-        fv[0] = (float)(av & 0xffu); fv[1] = (float)((av >> 8) & 0xffu);
-        fv[2] = (float)(bv & 0xffu); fv[3] = (float)((bv >> 8) & 0xffu);
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            fy[2 * r] = (float)((wy[j][r] >> s0) & 0xffu); fy[2 * r + 1] = (float)((wy[j][r] >> s1) & 0xffu);
+            fu[2 * r] = (float)((wu[j][r] >> s0) & 0xffu); fu[2 * r + 1] = (float)((wu[j][r] >> s1) & 0xffu);
+            fv[2 * r] = (float)((wv[j][r] >> s0) & 0xffu); fv[2 * r + 1] = (float)((wv[j][r] >> s1) & 0xffu);
+        }
 
         float t00[4], t10[4], t01[4], t11[4];
         if (yuv_range == CVGS_YUV_FULL) { // wave-uniform
@@ -257,12 +252,12 @@ __global__ __launch_bounds__(64 * kY422Waves) void k_yuv422_resize(const Y422Arg
         if (tile_rows) {
             // the lane = column register layout transposed through a wave-private LDS tile: lane l then owns 4 consecutive columns of row
             // l / 16 -- 16 bytes per lane and store instruction, three stores for the wave's four rows instead of twelve (as K4)
-            __shared__ __attribute__((aligned(16))) float tiles[kY422Waves][CN * RPW * kY422TileRow];
+            __shared__ __attribute__((aligned(16))) float tiles[kY444Waves][CN * RPW * kY444TileRow];
             float* const tile = tiles[wave];
 #pragma unroll
             for (int k = 0; k < CN; ++k)
 #pragma unroll
-                for (int j = 0; j < RPW; ++j) tile[(k * RPW + j) * kY422TileRow + lane] = tv[j][k];
+                for (int j = 0; j < RPW; ++j) tile[(k * RPW + j) * kY444TileRow + lane] = tv[j][k];
             __builtin_amdgcn_wave_barrier(); // (compiler ordering only: one wave's LDS operations run in order)
             typedef float f32x4t __attribute__((ext_vector_type(4)));
             typedef f32x4t f32x4t_a4 __attribute__((aligned(4)));
@@ -271,7 +266,7 @@ __global__ __launch_bounds__(64 * kY422Waves) void k_yuv422_resize(const Y422Arg
             float* const orow = (float*)out_base + (int64_t)z * img_stride + (int64_t)(row0 + i) * W + col_tile * 64 + q * 4;
 #pragma unroll
             for (int k = 0; k < CN; ++k) {
-                const f32x4t o = *(const f32x4t*)(tile + (k * RPW + i) * kY422TileRow + q * 4);
+                const f32x4t o = *(const f32x4t*)(tile + (k * RPW + i) * kY444TileRow + q * 4);
                 __builtin_nontemporal_store(o, (gf4)(orow + (int64_t)k * ch_stride));
             }
         }
@@ -279,33 +274,30 @@ __global__ __launch_bounds__(64 * kY422Waves) void k_yuv422_resize(const Y422Arg
 }
 
 // the family's traits for the shared launcher (k_yuv_family.hpp)
-hipError_t y422_launch_bf16(int prog, const ChainArgs& c, const PlaneParams* ip, int ni, const YuvFamGeom& g, const YuvFamMany& s, bool win);
-struct Y422Family {
-    using Geom = Y422Geom;
+hipError_t y444_launch_bf16(int prog, const ChainArgs& c, const PlaneParams* ip, int ni, const YuvFamGeom& g, const YuvFamMany& s, bool win);
+struct Y444Family {
+    using Geom = YuvFamGeom;
     template <int NPL, class Prog, typename OT, int RPW, int CN, bool WIN> static const void* kernel() {
-        return (const void*)&k_yuv422_resize<NPL, Prog, OT, RPW, CN, WIN>;
+        return (const void*)&k_yuv444_resize<NPL, Prog, OT, RPW, CN, WIN>;
     }
-    static bool eligible(const ReadArgs& r) {
-        return r.kind == CVGS_READ_NV12_RESIZE_LINEAR && (r.yuv_layout == CVGS_YUV_YUYV || r.yuv_layout == CVGS_YUV_UYVY);
-    }
-    CVGS_YUV_FAMILY_NAMES("k_yuv422_resize")
+    static bool eligible(const ReadArgs& r) { return r.kind == CVGS_READ_NV12_RESIZE_LINEAR && r.yuv_layout == CVGS_YUV_I444; }
+    CVGS_YUV_FAMILY_NAMES("k_yuv444_resize")
     static hipError_t launch_bf16(int prog, const ChainArgs& c, const PlaneParams* ip, int ni, const YuvFamGeom& g, const YuvFamMany& s, bool win) {
-        return y422_launch_bf16(prog, c, ip, ni, g, s, win);
+        return y444_launch_bf16(prog, c, ip, ni, g, s, win);
     }
 };
 
-// bf16 (CV_16BF) planar tensors: the fp16 instantiations' twins with OT = __bf16, compiled in k_yuv422_bf16.hip (this file included with
-// CVGS_Y422_BF16_TU, so the bf16 kernels build in parallel with the others).
-#ifdef CVGS_Y422_BF16_TU
-hipError_t y422_launch_bf16(int prog, const ChainArgs& c, const PlaneParams* ip, int ni, const YuvFamGeom& g, const YuvFamMany& s, bool win) {
-    return launch_yuv_fam_bf16<Y422Family>(prog, c, ip, ni, g, s, win);
+// bf16 (CV_16BF) planar tensors: the fp16 instantiations' twins with OT = __bf16, compiled in k_yuv444_bf16.hip (this file included with
+// CVGS_Y444_BF16_TU, so the bf16 kernels build in parallel with the others).
+#ifdef CVGS_Y444_BF16_TU
+hipError_t y444_launch_bf16(int prog, const ChainArgs& c, const PlaneParams* ip, int ni, const YuvFamGeom& g, const YuvFamMany& s, bool win) {
+    return launch_yuv_fam_bf16<Y444Family>(prog, c, ip, ni, g, s, win);
 }
 #else
-// launch_nv12's contract (it forwards the packed 4:2:2 layouts here): 1 launched / 0 not eligible / < 0 error.  Narrow rows take the
-// 4-byte window, so any plane width is served.
-int launch_yuv422(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_inline, LaunchCtx& ctx, bool dry_run, LaunchInfo* info) {
-    return launch_yuv_family<Y422Family>(c_in, inline_planes, n_inline, ctx, dry_run, info);
+// 1 launched / 0 not eligible / < 0 error (launch_nv12's contract).  Rows of one pixel take the 1-byte window, so any plane width is served.
+int launch_yuv444(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_inline, LaunchCtx& ctx, bool dry_run, LaunchInfo* info) {
+    return launch_yuv_family<Y444Family>(c_in, inline_planes, n_inline, ctx, dry_run, info);
 }
-#endif // CVGS_Y422_BF16_TU
+#endif // CVGS_Y444_BF16_TU
 
 } // namespace cvgs

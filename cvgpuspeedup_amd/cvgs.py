@@ -119,6 +119,28 @@ class GpuMat:
             raise ValueError("ROI outside the matrix")
         return GpuMat(h, w, self.cv_type, self.data + y * self.step + 2 * x, self.step, owner=self.owner)
 
+    @staticmethod
+    def from_yuv444_tensor(t):
+        """Wrap a planar 4:4:4 picture held as a uint8 torch tensor [3, H, W] (planes Y, U, V; stride(2) == 1): the CV_8UC1 luma view
+        with step = stride(1) and uv_offset = stride(0), the Y -> U and U -> V distance.  No alignment is needed."""
+        if t.dim() != 3 or t.shape[0] != 3 or str(t.dtype) != "torch.uint8" or t.stride(2) != 1:
+            raise ValueError("a planar 4:4:4 surface is a uint8 tensor [3, H, W] with stride(2) == 1")
+        m = GpuMat(t.shape[1], t.shape[2], make_type(DEPTH_8U, 1), t.data_ptr(), t.stride(1), owner=t)
+        m.uv_offset = int(t.stride(0))
+        return m
+
+    def yuv444_roi(self, x, y, w, h):
+        """Crop of a planar 4:4:4 surface (CV_8UC1 luma view that carries uv_offset, the distance between its planes): a plain view
+        at ANY origin and of any size >= 1 -- odd x, y, width and height included; uv_offset stays as it is."""
+        x, y, w, h = int(x), int(y), int(w), int(h)
+        if self.cv_type != make_type(DEPTH_8U, 1) or not getattr(self, "uv_offset", 0):
+            raise ValueError("planar 4:4:4 surfaces are CV_8UC1 luma views with uv_offset set (GpuMat.from_yuv444_tensor)")
+        if x < 0 or y < 0 or w < 1 or h < 1 or x + w > self.cols or y + h > self.rows:
+            raise ValueError("ROI outside the matrix")
+        m = GpuMat(h, w, self.cv_type, self.data + y * self.step + x, self.step, owner=self.owner)
+        m.uv_offset = self.uv_offset
+        return m
+
 
 def _scalar(vals, n=4):
     vals = list(vals) if hasattr(vals, "__len__") else [vals]
@@ -262,7 +284,8 @@ def read_nv12(mat, dsize=None, color_range=capi.YUV_FULL, primaries=capi.BT709, 
     BackIOp of fk::Resize<INTER_LINEAR> (reference tests/resize/test_fused_resize.cu:141-143).
     `mat` is the CV_8UC1 luma view (rows = luma height); the UV plane follows it in memory.  layout = YUV_P010: the luma
     view is CV_16UC1 (10-bit codes in the high bits of 16-bit samples) and R, G, B come out on the 0..1023 scale.
-    layout = YUV_YUYV / YUV_UYVY: `mat` is a packed 4:2:2 surface, CV_8UC2 (crops: GpuMat.yuv422_roi)."""
+    layout = YUV_YUYV / YUV_UYVY: `mat` is a packed 4:2:2 surface, CV_8UC2 (crops: GpuMat.yuv422_roi).
+    layout = YUV_I444: `mat` is the luma view of a planar 4:4:4 surface with uv_offset set (GpuMat.from_yuv444_tensor, yuv444_roi)."""
     kind = capi.READ_NV12 if dsize is None else capi.READ_NV12_RESIZE_LINEAR
     mats = [mat] if isinstance(mat, GpuMat) else list(mat)  # a list = N crops (GpuMat.nv12_roi) of decoder surfaces, one launch
     if layout in (capi.YUV_YUYV, capi.YUV_UYVY):
@@ -270,7 +293,7 @@ def read_nv12(mat, dsize=None, color_range=capi.YUV_FULL, primaries=capi.BT709, 
     else:
         src_type = make_type(DEPTH_16U if layout == capi.YUV_P010 else DEPTH_8U, 1)
     rd = ReadIOp(kind, src_type, mats, len(mats), dsize, IGNORE_AR, None, (color_range, primaries, 1 if alpha else 0))
-    rd.yuv_layout = layout  # fk::ReadYUV<PF>: NV12 (the reference's), NV21, I420, YV12, P010; packed 4:2:2: YUYV, UYVY
+    rd.yuv_layout = layout  # fk::ReadYUV<PF>: NV12 (the reference's), NV21, I420, YV12, P010; packed 4:2:2: YUYV, UYVY; planar 4:4:4: I444
     return rd
 
 
@@ -280,6 +303,13 @@ def read_yuv422(mat, dsize=None, color_range=capi.YUV_FULL, primaries=capi.BT709
     if layout not in (capi.YUV_YUYV, capi.YUV_UYVY):
         raise ValueError("read_yuv422 takes layout YUV_YUYV or YUV_UYVY")
     return read_nv12(mat, dsize, color_range, primaries, alpha, layout)
+
+
+def read_yuv444(mat, dsize=None, color_range=capi.YUV_FULL, primaries=capi.BT709, alpha=True):
+    """read_nv12 for planar 4:4:4 surfaces (I444: rocDecode's YUV444 output, rocJPEG's output for non-subsampled JPEGs): `mat` is the
+    CV_8UC1 luma view of the surface -- or a list of crops of it, at any origin -- with uv_offset set (GpuMat.from_yuv444_tensor,
+    GpuMat.yuv444_roi): U lies uv_offset bytes behind Y, V another uv_offset behind U, all three planes share `step`."""
+    return read_nv12(mat, dsize, color_range, primaries, alpha, capi.YUV_I444)
 
 
 def convertTo(in_type, out_type, alpha=None, beta=None):

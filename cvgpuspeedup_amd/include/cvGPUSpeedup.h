@@ -275,6 +275,35 @@ inline auto cvtColorUYVY(const cv::cuda::GpuMat& surf, const std::array<cv::Rect
     internal::yuv422_surface_crops(rd, surf, crops);
     return rd;
 }
+// cvtColorYUV444<cv::COLOR_YUV2RGB | cv::COLOR_YUV2BGR[, range, primaries, ALPHA]>(surf[, crops]): the same IOp for planar 4:4:4 surfaces
+// (I444: rocDecode's YUV444 output, rocJPEG's output for non-subsampled JPEGs).  `surf` is a CV_8UC1 GpuMat of 3 * H rows, the planes Y, U,
+// V stacked (as cvtColorNV12 takes H * 3 / 2 rows).  OpenCV has no RGBA code for this family, so alpha is a template bool.  Crops are
+// cv::Rects at ANY origin and of any size >= 1, odd values included.
+namespace internal {
+inline cvgs_image2d yuv444_view(const cv::cuda::GpuMat& surf, const cv::Rect& r) {
+    const int H = surf.rows / 3, step = (int)surf.step;
+    if (r.x < 0 || r.y < 0 || r.width < 1 || r.height < 1 || r.x + r.width > surf.cols || r.y + r.height > H)
+        throw std::runtime_error("planar 4:4:4 crop outside the surface");
+    return cvgs_image2d{surf.data + (size_t)r.y * step + (size_t)r.x, r.width, r.height, step, H * step};
+}
+} // namespace internal
+template <cv::ColorConversionCodes CODE, fk::ColorRange CR = fk::Full, fk::ColorPrimitives CP = fk::bt709, bool ALPHA = false, size_t N>
+inline auto cvtColorYUV444(const cv::cuda::GpuMat& surf, const std::array<cv::Rect, N>& crops) {
+    static_assert(CODE == cv::COLOR_YUV2RGB || CODE == cv::COLOR_YUV2BGR, "Color conversion type not supported yet.");
+    if (surf.type() != CV_8UC1 || surf.rows < 3 || surf.rows % 3 != 0)
+        throw std::runtime_error("cvtColorYUV444 needs a planar 4:4:4 surface (CV_8UC1 with rows = 3 * H: the planes Y, U, V stacked)");
+    using O = std::conditional_t<ALPHA, float4, float3>;
+    fk::RawPtr<fk::_2D, uchar> luma;
+    luma.data = (uchar*)surf.data;
+    luma.dims = {(uint)surf.cols, (uint)(surf.rows / 3), (uint)surf.step};
+    fk::YuvRead<fk::I444, CR, CP, ALPHA, O, CODE == cv::COLOR_YUV2BGR> rd{luma};
+    for (const cv::Rect& r : crops) rd.crops.push_back(internal::yuv444_view(surf, r)); // every view states its uv_offset, the whole surface too
+    return rd;
+}
+template <cv::ColorConversionCodes CODE, fk::ColorRange CR = fk::Full, fk::ColorPrimitives CP = fk::bt709, bool ALPHA = false>
+inline auto cvtColorYUV444(const cv::cuda::GpuMat& surf) {
+    return cvtColorYUV444<CODE, CR, CP, ALPHA>(surf, std::array<cv::Rect, 1>{cv::Rect(0, 0, surf.cols, surf.rows / 3)});
+}
 template <int INTER_F, fk::PixelFormat PF, fk::ColorRange CR, fk::ColorPrimitives CP, bool ALPHA, typename O, bool SW>
 inline auto resize(const fk::YuvRead<PF, CR, CP, ALPHA, O, SW>& nv12Read, const cv::Size& dsize) {
     static_assert(isSupportedInterpolation<INTER_F>, "Interpolation type not supported yet.");

@@ -72,6 +72,7 @@ enum ColorConversionCodes {
     COLOR_BGRA2RGBA = 5, COLOR_RGBA2BGRA = COLOR_BGRA2RGBA,
     COLOR_BGR2GRAY = 6, COLOR_RGB2GRAY = 7, COLOR_GRAY2BGR = 8, COLOR_GRAY2RGB = COLOR_GRAY2BGR,
     COLOR_GRAY2BGRA = 9, COLOR_GRAY2RGBA = COLOR_GRAY2BGRA, COLOR_BGRA2GRAY = 10, COLOR_RGBA2GRAY = 11,
+    COLOR_YUV2BGR = 84, COLOR_YUV2RGB = 85, // planar 4:4:4 surfaces: cvGS::cvtColorYUV444 (OpenCV's values)
     COLOR_YUV2RGB_NV12 = 90, COLOR_YUV2BGR_NV12 = 91, COLOR_YUV2RGBA_NV12 = 94, COLOR_YUV2BGRA_NV12 = 95,
     // packed 4:2:2 (OpenCV's values)
     COLOR_YUV2RGB_UYVY = 107, COLOR_YUV2BGR_UYVY = 108, COLOR_YUV2RGBA_UYVY = 111, COLOR_YUV2BGRA_UYVY = 112,

@@ -104,7 +104,8 @@ enum class CircularTensorOrder { NewestFirst = 0, OldestFirst = 1 };
 enum class ColorPlanes { Standard = 0, Transposed = 1 };
 // fk::PixelFormat: the reference's tests instantiate NV12 only; NV21 / I420 / YV12 / P010 (10-bit codes in 16-bit samples, the
 // result on the 0..1023 scale) are this engine's further 4:2:0 readers (numeric values = cvgs_yuv_layout)
-enum PixelFormat { NV12 = 0, NV21 = 1, I420 = 2, YV12 = 3, P010 = 4, YUYV = 5, UYVY = 6 }; // YUYV / UYVY: packed 4:2:2, CV_8UC2 surfaces (cvgs_yuv_layout)
+// YUYV / UYVY: packed 4:2:2, CV_8UC2 surfaces; I444: planar 4:4:4, three full-resolution CV_8UC1 planes uv_offset apart (cvgs_yuv_layout)
+enum PixelFormat { NV12 = 0, NV21 = 1, I420 = 2, YV12 = 3, P010 = 4, YUYV = 5, UYVY = 6, I444 = 7 };
 enum ColorRange { Full = 0, Limited = 1 };
 enum ColorPrimitives { bt601 = 0, bt709 = 1, bt2020 = 2 };
 template <PixelFormat PF> using YuvSample = std::conditional_t<PF == P010, unsigned short, unsigned char>;

@@ -163,10 +163,25 @@ typedef enum cvgs_yuv_primaries { CVGS_BT601 = 0, CVGS_BT709 = 1, CVGS_BT2020 = 
  * width >= 1, any height >= 1.  A view of odd width reads the whole last pair: the bytes a plane may read are
  * [0, 4 * ceil(width / 2)) of each of its rows, and nothing outside them is read; cvgs_plane_table_hull and the independence
  * check of cvgs_execute_many use that range.  Device plane tables: CVGS_ERR_UNSUPPORTED (a table carries no layout tag).  */
+/* Planar 4:4:4 (I444: rocDecode's YUV444 surfaces of 4:4:4 HEVC / AV1 streams, rocJPEG's output for non-subsampled JPEGs), accepted
+ * by both NV12 read kinds: three full-resolution planes Y, U, V that share `step`.
+ * src_type is CV_8UC1; width / height in pixels, any value >= 1, odd included; step >= width; NO alignment requirement on data,
+ * step or uv_offset.  `data` points at Y(0,0) of the view, uv_offset is the byte distance from Y(0,0) to U(0,0) of the same view,
+ * and V(0,0) lies the same distance behind U(0,0): V = data + 2 * uv_offset.  A whole rocDecode surface: uv_offset = pitch *
+ * aligned_height; a [3, H, W] tensor: step = stride(1), uv_offset = stride(0).  uv_offset must ALWAYS be stated -- there is no
+ * "0 = height * step" default, a crop and a whole surface are described the same way: uv_offset == 0 and
+ * uv_offset < (height - 1) * step + width (the planes of the view would overlap) are CVGS_ERR_INVALID, uv_offset > 2^30 is
+ * CVGS_ERR_UNSUPPORTED.  A crop is a plain view at ANY (x, y, w, h): data = Y + y*step + x, uv_offset unchanged.
+ * Pixel (x, y) is Y[y][x], U[y][x], V[y][x]; conversion (range, primaries, alpha, fp32 operation order) and the bilinear blend are
+ * those of the 8-bit 4:2:0 layouts, unchanged: each tap is converted, then the taps are blended.  A plane reads the bytes
+ * [0, width) of each of its `height` rows in each of the three planes, and nothing else; cvgs_plane_table_hull and the
+ * independence check of cvgs_execute_many use [data, data + 2 * uv_offset + (height - 1) * step + width).  Device plane tables:
+ * CVGS_ERR_UNSUPPORTED (a table carries no layout tag).                                                                          */
 typedef enum cvgs_yuv_layout {
     CVGS_YUV_NV12 = 0, CVGS_YUV_NV21 = 1, CVGS_YUV_I420 = 2, CVGS_YUV_YV12 = 3, CVGS_YUV_P010 = 4,
     CVGS_YUV_YUYV = 5, /* bytes Y0 U Y1 V per pixel pair (YUY2, V4L2 YUYV) */
-    CVGS_YUV_UYVY = 6  /* bytes U Y0 V Y1 per pixel pair                   */
+    CVGS_YUV_UYVY = 6, /* bytes U Y0 V Y1 per pixel pair                   */
+    CVGS_YUV_I444 = 7  /* planar 4:4:4: full-resolution planes Y, U, V     */
 } cvgs_yuv_layout;
 
 #define CVGS_READ_FLAG_TABLE_ON_DEVICE 1u /* `src` is a device table made by cvgs_plane_table_build */

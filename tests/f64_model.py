@@ -403,6 +403,8 @@ def _cast(x, dst, truncating, sw):
             return Val(x.v, x.b + U * (np.abs(x.v) + x.b), dst)
         return Val(x.v, x.b, dst)  # 8- and 16-bit integers and 16-bit floats widen exactly
     if dst == DEPTH_64F:
+        if src == DEPTH_32F:
+            return Val(x.v, x.b, dst)  # every fp32 value is a double: exact, no bound added (64F ARITHMETIC stays outside the model)
         raise NotImplementedError("CV_64F chains are outside the model")
     lo, hi = INT_RANGE[dst]
     if src in INT_RANGE:

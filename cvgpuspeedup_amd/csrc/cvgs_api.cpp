@@ -871,11 +871,12 @@ struct Upload {
     ~Upload() { done(false); }
 };
 
-// The resize kernel family of a decode-side chain: planar 4:4:4 has its own (k_yuv444.hip: any plane width); every other layout is
-// launch_nv12's business.  1 launched / 0 not eligible / < 0 error.
+// The resize kernel family of a decode-side chain, by its layout: planar 4:4:4 (k_yuv444.hip) and packed 4:2:2 (k_yuv422.hip) serve any
+// plane width; the 4:2:0 layouts are K4's (k_nv12.hip), which wants min_width >= 4.  1 launched / 0 not eligible / < 0 error.
 int launch_yuv_resize(const ChainArgs& c, const PlaneParams* inline_planes, int n_inline, int min_width, LaunchCtx& ctx, bool dry_run, LaunchInfo* info,
                       uint32_t chain_flags = 0) {
     if (is_yuv444(c.read.yuv_layout)) return launch_yuv444(c, inline_planes, n_inline, ctx, dry_run, info);
+    if (is_yuv422(c.read.yuv_layout)) return launch_yuv422(c, inline_planes, n_inline, ctx, dry_run, info);
     return launch_nv12(c, inline_planes, n_inline, min_width, ctx, dry_run, info, chain_flags);
 }
 // stretch geometry on every plane, and rows the family's tap window fits into (K4, 4:2:2: k4_planes_eligible; 4:4:4: any width)

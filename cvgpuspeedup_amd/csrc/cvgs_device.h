@@ -217,18 +217,18 @@ static constexpr int64_t kX4MinWaveRows = 12288; // output rows x 64-column tile
 int launch_generic64(const ChainArgs& c, const Prog64Args& p64, const PlaneParams* inline_planes, int n_inline, void* stream,
                      bool dry_run, LaunchInfo* info);
 
-// K4 fast path: NV12 read-back fused into the bilinear resize -> program -> planar fp32 tensor or packed pixels.
+// K4 fast path: NV12 read-back fused into the bilinear resize -> program -> planar fp32 tensor or packed pixels.  The 4:2:0 layouts
+// (NV12 / NV21, P010, I420 / YV12); the three families below run ONE launcher (k_yuv_family.hpp), and cvgs_api.cpp (launch_yuv_resize)
+// picks the family from the layout.  1 launched / 0 not eligible / < 0 error.
 int launch_nv12(const ChainArgs& c, const PlaneParams* inline_planes, int n_inline, int min_width, LaunchCtx& ctx, bool dry_run, LaunchInfo* info,
                 uint32_t chain_flags = 0);
 // K4 at frame size, two output pixels per lane (k_nv12_x2.hip); 1 launched / 0 not eligible / < 0 error
 int launch_nv12_x2(const ChainArgs& c, const PlaneParams* planes, int n_planes, bool prog_swap, void* stream, bool dry_run);
 static constexpr int64_t kK4X2MinWaveRows = 4096; // output rows x 64-column tiles x surfaces from which launch_nv12 prefers it
 bool k4_planes_eligible(const PlaneParams* planes, int n, int dst_w, int dst_h);
-// Packed 4:2:2 surfaces (YUYV / UYVY) read back inside the bilinear resize (k_yuv422.hip): K4's targets and dispatch rules; launch_nv12
-// forwards the two layouts here, so every caller of launch_nv12 serves them.  1 launched / 0 not eligible / < 0 error.
+// Packed 4:2:2 surfaces (YUYV / UYVY) read back inside the bilinear resize (k_yuv422.hip): K4's targets and dispatch rules, any plane width.
 int launch_yuv422(const ChainArgs& c, const PlaneParams* inline_planes, int n_inline, LaunchCtx& ctx, bool dry_run, LaunchInfo* info);
-// Planar 4:4:4 surfaces (I444) read back inside the bilinear resize (k_yuv444.hip): the same targets and rules -- both families run the
-// launcher of k_yuv_family.hpp.  launch_nv12 does not know the layout: cvgs_api.cpp sends such chains here.
+// Planar 4:4:4 surfaces (I444) read back inside the bilinear resize (k_yuv444.hip): the same targets and rules, any plane width.
 int launch_yuv444(const ChainArgs& c, const PlaneParams* inline_planes, int n_inline, LaunchCtx& ctx, bool dry_run, LaunchInfo* info);
 
 // Thread-fused pointwise chains on u8 sources (4 pixels per thread) -> fp32 planar / packed.

@@ -8,11 +8,7 @@
 // pixel and source row: ONE unaligned 2-byte load brings both luma taps, ONE unaligned 4-byte load both chroma
 // pairs (4 loads per pixel instead of 12 byte loads); windows are clamped into the row.  Planar stores are
 // full-wave 256-byte rows, non-temporal.
-#include <cstdlib>
-#include <memory>
-#include <type_traits>
-
-#include "k_taps.hpp"
+#include "k_yuv_family.hpp"
 
 namespace cvgs {
 
@@ -23,27 +19,8 @@ typedef const __attribute__((address_space(1))) u32_unaligned* gptr_u32;
 typedef uint64_t u64_unaligned __attribute__((aligned(1)));
 typedef const __attribute__((address_space(1))) u64_unaligned* gptr_u64;
 
-struct N12Geom {
-    int32_t dst_w, dst_h, out_w, cn; // cn: 3, or 4 with alpha
-    int64_t img_stride, ch_stride;
-    uint8_t* out;
-    int32_t out_step; // packed 2D writes: bytes per row
-    int32_t packed;   // 0: planar fp32 tensor, 1: packed pixels through the generic write stage
-    // optional second planar target with its own strides (CircularTensor push: history ring + ordered tensor)
-    uint8_t* out2;
-    int64_t img_stride2, ch_stride2;
-    uint32_t col_tiles; // NPL == 0 (fused chains): blockIdx.x = row group * col_tiles + column tile
-    uint32_t pad;
-    // fused launches with host descriptors (NPL == 0; cvgs_api.cpp: ManyPool): the first work-item stores done_value into *done_word
-    // (pinned host memory) when the kernel starts -- every earlier launch of the stream has finished by then (as K1: k_k1_impl.hpp)
-    uint64_t* done_word;
-    uint64_t done_value;
-};
-
-// NPL > 0: the planes travel in the kernel arguments, grid = (column tiles, row groups, planes).  NPL == 0: the chains of a
-// cvgs_execute_many launch, planes in per-chain device tables, grid = (column tiles x row groups, planes, chains).
-// NPL < 0: the segments with the planes of ALL chains inside the kernel arguments (KernArgsManyInline<-NPL>: fused chains described on the host, as K1).
-template <int NPL> using K4Args = std::conditional_t<NPL == 0, KernArgsMany, std::conditional_t<(NPL < 0), KernArgsManyInline<(NPL < 0 ? -NPL : 1)>, KernArgs<(NPL > 0 ? NPL : 1)>>>;
+struct N12Geom : YuvFamGeom {}; // (a type of its own: part of the kernels' signature)
+template <int NPL> using K4Args = YuvFamArgs<NPL>;
 
 // waves per workgroup (see k_k1.hip): an A/B build may override it
 #ifndef CVGS_K4_WPB
@@ -52,9 +29,7 @@ template <int NPL> using K4Args = std::conditional_t<NPL == 0, KernArgsMany, std
 constexpr int kK4Waves = CVGS_K4_WPB;
 constexpr int kK4TileRow = 80; // floats between the rows of a wave's LDS tile (64 + padding: the 16-byte reads of a row group do not collide)
 
-using N12SwapMulSubDiv = ProgSwapMulSubDiv; // the compile-time program of k_taps.hpp (incl. the division by the uniform divisor)
-
-// RPW output rows per wave (the launcher uses 1, see launch_n12); CN output channels (3, or 4 with alpha).  One tap's conversion:
+// RPW output rows per wave (the launcher uses 1, see launch_yuv_fam_rows); CN output channels (3, or 4 with alpha).  One tap's conversion:
 // k4_tap (k_common.hpp), shared with the descriptor queue's NV12 worker (k_queue.hip).
 // S16: P010 -- the same geometry with 16-bit samples (10-bit code = sample >> 6): the two luma taps are ONE 4-byte load, the
 // two chroma pairs ONE 8-byte load.
@@ -410,292 +385,69 @@ __global__ __launch_bounds__(64 * kK4Waves) void k4_nv12_resize(const K4Args<NPL
     }
 }
 
-// what launch_nv12 hands to the instantiation it picks: the call's LaunchCtx and the chains of a cvgs_execute_many launch
-struct N12Many {
-    LaunchCtx* ctx;
-    const ManySeg* segs;
-    int n_segs;
-    const PlaneParams* planes; // host-described fused chains whose planes travel in the kernel arguments (segs[i].table = first index), or null
-    int n_planes;
+// the family's traits for the shared launcher (k_yuv_family.hpp): one family per kernel variant -- interleaved 8-bit chroma (NV12 / NV21),
+// S16 (P010), PL (I420 / YV12) --, picked from the layout by k4_pick
+static_assert(kK4Waves == kYuvFamWaves, "the shared launcher sizes K4's block and grid with kYuvFamWaves: a CVGS_K4_WPB build needs its own");
+hipError_t k4_launch_bf16(int prog, const ChainArgs& c, const PlaneParams* ip, int ni, const YuvFamGeom& g, const YuvFamMany& s, bool win);
+struct K4FamilyBase : YuvFamDefaults {
+    using Geom = N12Geom;
+    static bool eligible(const ReadArgs& r) { return r.kind == CVGS_READ_NV12_RESIZE_LINEAR; } // (launch_nv12 is handed the 4:2:0 layouts only)
+    CVGS_YUV_FAMILY_NAMES("k4_nv12_resize")
+    static hipError_t launch_bf16(int prog, const ChainArgs& c, const PlaneParams* ip, int ni, const YuvFamGeom& g, const YuvFamMany& s, bool win) {
+        return k4_launch_bf16(prog, c, ip, ni, g, s, win);
+    }
+    // whole surfaces stretched into large targets (cfg #3: 6K -> 1280 x 720): two output pixels per lane (k_nv12_x2.hip) once the
+    // launch is paced by instruction issue rather than by its latency; CVGS_CHAIN_NO_THREAD_FUSION keeps the one-pixel kernel
+    static int frame_kernel(const ChainArgs& c, const PlaneParams* planes, int n, bool prog_swap, bool f16, const LaunchCtx& ctx, uint32_t chain_flags,
+                            bool dry_run, LaunchInfo* info) {
+        const ReadArgs& r = c.read;
+        if (f16 || ctx.segs || r.out_cn != 3 || (chain_flags & CVGS_CHAIN_NO_THREAD_FUSION)) return 0;
+        const char* x2_env = getenv("CVGS_K4_X2"); // tuning / test hook: 0 = never, 1 = whenever eligible
+        const int64_t wave_rows = (int64_t)r.batch * r.dst_h * ((r.dst_w + 63) / 64);
+        if (!(x2_env ? x2_env[0] == '1' : wave_rows >= kK4X2MinWaveRows)) return 0;
+        const int rc = launch_nv12_x2(c, planes, n, prog_swap, ctx.stream, dry_run);
+        if (rc != 0 && info) info->kernel = prog_swap ? "k4_nv12_x2_swap_mul_sub_div" : "k4_nv12_x2_mul_sub_div";
+        return rc;
+    }
 };
-
-template <class Prog, typename OT, int RPW, int CN, bool S16, bool WIN = false, bool PL = false>
-static hipError_t launch_n12_r(const ChainArgs& c, const PlaneParams* ip, int ni, const N12Geom& g_in, const N12Many& many) {
-    hipStream_t s = (hipStream_t)many.ctx->stream;
-    N12Geom g = g_in;
-    const uint32_t col_tiles = (uint32_t)((g.dst_w + 63) / 64), row_groups = (uint32_t)((g.dst_h + kK4Waves * RPW - 1) / (kK4Waves * RPW));
-    g.col_tiles = col_tiles;
-    g.pad = 0;
-    g.done_word = nullptr;
-    g.done_value = 0;
-    constexpr bool kImage = std::is_same_v<OT, uint8_t>; // packed u8 images: never fused chains, never the 16 KB argument block
-    if constexpr (!kImage && !PL && !WIN) if (many.segs && many.planes) {
-        // host descriptors of at most kManyInlineLarge planes: segments + planes in the arguments (16 KB / 52 KB blocks), capturable
-        const dim3 grid(col_tiles * row_groups, (unsigned)c.read.batch, (unsigned)many.n_segs);
-        auto go = [&](auto cap_tag) {
-            constexpr int CAP = decltype(cap_tag)::value;
-            // the 16 KB / 52 KB argument block: staged in a per-thread heap buffer, handed over by address (as K1's: k_k1_impl.hpp launch_t)
-            static thread_local std::unique_ptr<KernArgsManyInline<CAP>> staged;
-            if (!staged) staged.reset(new KernArgsManyInline<CAP>());
-            KernArgsManyInline<CAP>& a = *staged;
-            a.c = c;
-            for (int i = 0; i < CVGS_MAX_CHAINS; ++i) a.seg[i] = i < many.n_segs ? many.segs[i] : ManySeg{nullptr, nullptr, 0, 0};
-            for (int i = 0; i < many.n_planes && i < CAP; ++i) a.planes[i] = many.planes[i];
-            void* args[] = {(void*)&a, (void*)&g};
-            (void)hipLaunchKernel((const void*)&k4_nv12_resize<-CAP, Prog, OT, RPW, CN, S16, WIN, PL>, grid, dim3(64 * kK4Waves), args, 0, s);
-        };
-        if (many.n_planes <= kManyInlineSmall) go(std::integral_constant<int, kManyInlineSmall>{});
-        else go(std::integral_constant<int, kManyInlineLarge>{});
-        return hipGetLastError();
+template <bool S16, bool PL> struct K4Family : K4FamilyBase {
+    template <int NPL, class Prog, typename OT, int RPW, int CN, bool WIN> static const void* kernel() {
+        return (const void*)&k4_nv12_resize<NPL, Prog, OT, RPW, CN, S16, WIN, PL>;
     }
-    if constexpr (!kImage) if (many.segs) {
-        KernArgsMany a;
-        a.c = c;
-        for (int i = 0; i < CVGS_MAX_CHAINS; ++i) a.seg[i] = i < many.n_segs ? many.segs[i] : ManySeg{nullptr, nullptr, 0, 0};
-        LaunchCtx& x = *many.ctx;
-        if (x.done_word && !x.done_word_taken) {
-            x.done_word_taken = true;
-            g.done_word = x.done_word;
-            g.done_value = x.done_value;
-        }
-        const dim3 grid(col_tiles * row_groups, (unsigned)c.read.batch, (unsigned)many.n_segs);
-        hipLaunchKernelGGL((k4_nv12_resize<0, Prog, OT, RPW, CN, S16, WIN, PL>), grid, dim3(64 * kK4Waves), 0, s, a, g);
-        return hipGetLastError();
-    }
-    const dim3 grid(col_tiles, row_groups, c.read.batch);
-    if (ni <= 8) {
-        KernArgs<8> a;
-        a.c = c;
-        for (int i = 0; i < 8; ++i) a.planes[i] = i < ni ? ip[i] : PlaneParams{};
-        hipLaunchKernelGGL((k4_nv12_resize<8, Prog, OT, RPW, CN, S16, WIN, PL>), grid, dim3(64 * kK4Waves), 0, s, a, g);
-    } else if (ni <= CVGS_KERNARG_PLANES) { // crop lists of a decoder surface: up to CVGS_KERNARG_PLANES descriptors in the kernel arguments
-        KernArgs<CVGS_KERNARG_PLANES> a;
-        a.c = c;
-        for (int i = 0; i < CVGS_KERNARG_PLANES; ++i) a.planes[i] = i < ni ? ip[i] : PlaneParams{};
-        hipLaunchKernelGGL((k4_nv12_resize<CVGS_KERNARG_PLANES, Prog, OT, RPW, CN, S16, WIN, PL>), grid, dim3(64 * kK4Waves), 0, s, a, g);
-    } else if constexpr (!kImage) { // ... up to CVGS_KERNARG_PLANES_MAX in a 16 KB argument block (see cvgs_device.h: cheaper than a table for an eager call)
-        KernArgs<kKernargPlanesBig> a;
-        a.c = c;
-        for (int i = 0; i < kKernargPlanesBig; ++i) a.planes[i] = i < ni ? ip[i] : PlaneParams{};
-        hipLaunchKernelGGL((k4_nv12_resize<kKernargPlanesBig, Prog, OT, RPW, CN, S16, WIN, PL>), grid, dim3(64 * kK4Waves), 0, s, a, g);
-    }
-    return hipGetLastError();
-}
-
-// the channel count (3, or 4 with alpha) becomes a template argument
-template <class Prog, typename OT, bool S16, bool WIN, bool PL>
-static hipError_t launch_n12_cn(const ChainArgs& c, const PlaneParams* ip, int ni, const N12Geom& g, const N12Many& s) {
-    if (g.cn == 4) return launch_n12_r<Prog, OT, 1, 4, S16, WIN, PL>(c, ip, ni, g, s);
-    return launch_n12_r<Prog, OT, 1, 3, S16, WIN, PL>(c, ip, ni, g, s);
-}
-
-template <class Prog, typename OT = float>
-static hipError_t launch_n12(const ChainArgs& c, const PlaneParams* ip, int ni, const N12Geom& g, const N12Many& s, bool win = false) {
-    const bool pl = c.read.yuv_layout == CVGS_YUV_I420 || c.read.yuv_layout == CVGS_YUV_YV12;
-    const bool s16 = c.read.yuv_layout == CVGS_YUV_P010;
-    if (win) { // aspect-ratio windows / default-value planes: their own instantiations (see k4_nv12_resize)
-        if (pl) return launch_n12_cn<Prog, OT, false, true, true>(c, ip, ni, g, s);
-        if (s16) return launch_n12_cn<Prog, OT, true, true, false>(c, ip, ni, g, s);
-        return launch_n12_cn<Prog, OT, false, true, false>(c, ip, ni, g, s);
-    }
-    // One output row per wave.  Two rows per wave were measured for whole-frame outputs (cfg #3: 14400 one-row waves need two
-    // rounds of the chip's 8192 wave slots) and lost: 8.27 vs 8.08 us, and 5.29 vs 4.52 us on 50 crops -- the launch is
-    // bound by the VALU work per row (~100 instructions x 14 waves per SIMD) plus the launch floor, not by residency.
-    // launches in the throughput regime (cvgs_execute_many: the crops of several surfaces; one chain of hundreds of crops): four rows per wave, the rows leaving as
-    // 16-byte stores through a wave-private LDS tile -- the launch is bound by its memory INSTRUCTIONS (four tap loads per row and lane):
-    // 16 x 50 crops of NV12 surfaces 52 -> see profiles/r05_x_k4_tick_rows4.txt
-    if constexpr (std::is_same_v<OT, float>) {
-        const N12Many& many = s;
-        if (g.cn == 3 && !pl) { // (a single chain of 256+ crops is in the same regime; P010 surfaces too)
-            int64_t planes = many.segs ? 0 : c.read.batch;
-            for (int i = 0; many.segs && i < many.n_segs; ++i) planes += many.segs[i].batch;
-            if (planes * g.dst_h * ((g.dst_w + 63) / 64) >= 32768)
-                return s16 ? launch_n12_r<Prog, OT, 4, 3, true>(c, ip, ni, g, s) : launch_n12_r<Prog, OT, 4, 3, false>(c, ip, ni, g, s);
-        }
-    }
-    if (pl) return launch_n12_cn<Prog, OT, false, false, true>(c, ip, ni, g, s);
-    if (s16) return launch_n12_cn<Prog, OT, true, false, false>(c, ip, ni, g, s);
-    return launch_n12_cn<Prog, OT, false, false, false>(c, ip, ni, g, s);
+    // planar chroma: one row per wave at every size, and fused chains through device tables only (no instantiations for either)
+    static constexpr bool kRows4 = !PL, kManyInline = !PL;
+};
+template <class Fn> static auto k4_pick(int yuv_layout, Fn fn) {
+    if (yuv_layout == CVGS_YUV_I420 || yuv_layout == CVGS_YUV_YV12) return fn(K4Family<false, true>{});
+    if (yuv_layout == CVGS_YUV_P010) return fn(K4Family<true, false>{});
+    return fn(K4Family<false, false>{});
 }
 
 // bf16 (CV_16BF) planar tensors: the fp16 instantiations' twins with OT = __bf16, compiled in k_nv12_bf16.hip (this file included with
-// CVGS_K4_BF16_TU, so the bf16 kernels build in parallel with the others).  prog: 0 swap-mul-sub-div, 1 canonical, 2 interpreted.
-hipError_t k4_launch_bf16(int prog, const ChainArgs& c, const PlaneParams* ip, int ni, const N12Geom& g, const N12Many& s, bool win);
+// CVGS_K4_BF16_TU, so the bf16 kernels build in parallel with the others).
 #ifdef CVGS_K4_BF16_TU
-hipError_t k4_launch_bf16(int prog, const ChainArgs& c, const PlaneParams* ip, int ni, const N12Geom& g, const N12Many& s, bool win) {
-    return prog == 0 ? launch_n12<N12SwapMulSubDiv, __bf16>(c, ip, ni, g, s, win)
-                     : (prog == 1 ? launch_n12<K1CanonProg, __bf16>(c, ip, ni, g, s, win) : launch_n12<InterpProg, __bf16>(c, ip, ni, g, s, win));
+hipError_t k4_launch_bf16(int prog, const ChainArgs& c, const PlaneParams* ip, int ni, const YuvFamGeom& g, const YuvFamMany& s, bool win) {
+    return k4_pick(c.read.yuv_layout, [&](auto f) { return launch_yuv_fam_bf16<decltype(f)>(prog, c, ip, ni, g, s, win); });
 }
 #else
-// Returns 1 if it took the chain, 0 if not eligible, <0 on error.
-// Can K4 serve these planes?  Rows wide enough for the 4-byte chroma window; stretch geometry for the callers that cannot pick
-// the windowed instantiation (fused chains, staged tables).
-bool k4_planes_eligible(const PlaneParams* planes, int n, int dst_w, int dst_h) { // stretch geometry: the WIN = false instantiations
-    for (int i = 0; i < n; ++i) {
-        const PlaneParams& P = planes[i];
-        if (P.w < 4 || P.x1 != 0 || P.y1 != 0 || P.x2 != dst_w - 1 || P.y2 != dst_h - 1) return false;
-    }
-    return true;
-}
-static bool k4_planes_wide_enough(const PlaneParams* planes, int n) {
+// Stretch geometry on rows wide enough for the 4-byte chroma window: what the callers that cannot pick the windowed instantiations
+// (fused chains, staged tables) check on their planes.
+bool k4_planes_eligible(const PlaneParams* planes, int n, int dst_w, int dst_h) {
     for (int i = 0; i < n; ++i)
         if (planes[i].w < 4) return false;
-    return true;
+    return yuv_fam_stretch(planes, n, dst_w, dst_h);
 }
 
-// ctx.segs (n_segs >= 1): the chains of a cvgs_execute_many launch -- their planes live in device tables that the caller
-// has checked with k4_planes_eligible; c_in.read.batch is the largest batch.  nullptr: one chain (inline_planes).
-int launch_nv12(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_inline, int min_width, LaunchCtx& ctx, bool dry_run, LaunchInfo* info,
+// The 4:2:0 layouts through the shared launcher: 1 launched / 0 not eligible / < 0 error.  min_width: over the planes that are read;
+// narrower rows than the chroma window are the generic kernel's (fused chains: the caller has checked them with k4_planes_eligible).
+int launch_nv12(const ChainArgs& c, const PlaneParams* inline_planes, int n_inline, int min_width, LaunchCtx& ctx, bool dry_run, LaunchInfo* info,
                 uint32_t chain_flags) {
-    const ManySeg* const segs = ctx.segs;
-    const int n_segs = ctx.n_segs;
-    void* const stream = ctx.stream;
-    const ReadArgs& r = c_in.read;
-    if (r.yuv_layout == CVGS_YUV_YUYV || r.yuv_layout == CVGS_YUV_UYVY) // packed 4:2:2: its own kernel family (k_yuv422.hip), any plane width
-        return launch_yuv422(c_in, inline_planes, n_inline, ctx, dry_run, info);
-    // fp16 / bf16 planar tensors: the trailing CAST(CV_16F / CV_16BF) moves into the store (a bf16 chain of any other shape: the
-    // interpreted kernel); "f16" below means "a 16-bit float store" from here on
-    const bool planar_kind = c_in.write.kind == CVGS_WRITE_TENSOR_SPLIT || c_in.write.kind == CVGS_WRITE_TENSOR_T_SPLIT;
-    const bool trailing_cast = c_in.prog.n >= 1 && c_in.prog.opcode[c_in.prog.n - 1] == CVGS_OP_CAST;
-    const bool bf16 = planar_kind && c_in.write.depth == kDepthBF16 && trailing_cast;
-    if (chain_has_bf16(c_in) && !bf16) return 0;
-    const bool f16 = planar_kind && (c_in.write.depth == CVGS_DEPTH_16F || bf16) && trailing_cast;
-    ChainArgs c_cut;
-    if (f16) {
-        c_cut = c_in;
-        c_cut.prog.n -= 1;
-        for (int k = 0; k < c_cut.prog.n; ++k)
-            if (c_cut.prog.opcode[k] == CVGS_OP_CAST || c_cut.prog.opcode[k] == CVGS_OP_CAST_TRUNC) return 0;
+    if (!ctx.segs) {
+        if (min_width < 4) return 0;
+        for (int i = 0; i < n_inline && i < c.read.used; ++i)
+            if (inline_planes[i].w < 4) return 0;
     }
-    const ChainArgs& c = f16 ? c_cut : c_in;
-    if (r.kind != CVGS_READ_NV12_RESIZE_LINEAR) return 0;
-    if (segs) {
-        if (n_segs < 1 || n_segs > CVGS_MAX_CHAINS || c_in.write.data2) return 0;
-        // segments without a table: the planes travel in the kernel arguments -- interleaved chroma only (launch_n12_r)
-        if (!r.table && (!inline_planes || n_inline < 1 || n_inline > kManyInlineLarge || (r.yuv_layout != CVGS_YUV_NV12 && r.yuv_layout != CVGS_YUV_NV21 && r.yuv_layout != CVGS_YUV_P010))) return 0;
-    } else {
-        if (r.table || n_inline > kKernargPlanesBig || min_width < 4) return 0; // tiny frames / resident tables: generic kernel
-        if (n_inline > CVGS_KERNARG_PLANES && !(planar_kind && (c_in.write.depth == CVGS_DEPTH_32F || f16))) return 0; // the large block: tensors only
-        if (!k4_planes_wide_enough(inline_planes, r.used < n_inline ? r.used : n_inline)) return 0;
-    }
-    if (r.batch > 65535) return 0;
-    const WriteArgs& w = c.write;
-    const bool planar = planar_kind && (w.depth == CVGS_DEPTH_32F || f16);
-    const bool packed = w.kind == CVGS_WRITE_PIXEL_2D || w.kind == CVGS_WRITE_PIXEL_3D;
-    if (!planar && !packed) return 0;
-    if (segs && !planar) return 0; // fused chains: planar tensors only
-
-    // packed u8 C3 images (decoder surface -> thumbnail / display image): resize -> [REORDER / MUL / ADD / SUB / DIV in float] ->
-    // CAST(CV_8U) -> write.  The trailing SaturateCast becomes the store's conversion and the store a coalesced tile.
-    bool u8img = false;
-    int u8_prog = 2; // 0: nothing in front of the cast, 1: the R<->B swap only, 2: interpreted
-    ChainArgs c8 = c;
-    // the reference's spelling casts first and reorders the bytes afterwards (SaturateCast<float4, uchar4> -> VectorReorder<uchar4, 2, 1, 0, 3>);
-    // a pure permutation commutes with the per-channel cast, so the cast moves to the end (bit for bit the same image)
-    if (c8.prog.n >= 2 && c8.prog.opcode[c8.prog.n - 1] == CVGS_OP_REORDER && c8.prog.opcode[c8.prog.n - 2] == CVGS_OP_CAST &&
-        c8.prog.aux[c8.prog.n - 2] == CVGS_DEPTH_8U) {
-        const int a = c8.prog.n - 2, b = c8.prog.n - 1;
-        std::swap(c8.prog.opcode[a], c8.prog.opcode[b]);
-        std::swap(c8.prog.aux[a], c8.prog.aux[b]);
-        for (int k = 0; k < 4; ++k) std::swap(c8.prog.operand[a][k], c8.prog.operand[b][k]);
-    }
-    if (packed && !f16 && !segs && w.depth == CVGS_DEPTH_8U && n_inline <= CVGS_KERNARG_PLANES && c8.prog.n >= 1 &&
-        c8.prog.opcode[c8.prog.n - 1] == CVGS_OP_CAST && c8.prog.aux[c8.prog.n - 1] == CVGS_DEPTH_8U) {
-        u8img = true;
-        for (int k = 0; k + 1 < c8.prog.n; ++k) {
-            const int op = c8.prog.opcode[k];
-            const bool arith = op == CVGS_OP_MUL || op == CVGS_OP_ADD || op == CVGS_OP_SUB || op == CVGS_OP_DIV || op == CVGS_OP_REORDER || op == CVGS_OP_NOP;
-            if (!arith && !(op == CVGS_OP_CAST && c8.prog.aux[k] == CVGS_DEPTH_32F)) u8img = false; // the value stays out_cn floats up to the cast
-        }
-        const int swap_rb = r.out_cn == 3 ? (2 | (1 << 2) | (0 << 4)) : (2 | (1 << 2) | (0 << 4) | (3 << 6));
-        if (c8.prog.n == 1) u8_prog = 0;
-        else if (c8.prog.n == 2 && c8.prog.opcode[0] == CVGS_OP_REORDER && c8.prog.aux[0] == swap_rb) u8_prog = 1;
-    }
-    if (u8img) {
-        c8.prog.n -= 1;
-        c8.prog.fast_div = 0;
-        bool canon8 = false; // brightness / contrast on the way to a u8 image, ...: the canonical arithmetic program (k_taps.hpp)
-        if (u8_prog == 2) {
-            ProgArgs canon;
-            if (k1_canonicalise(c8.prog, r.out_cn, canon)) {
-                c8.prog = canon;
-                canon8 = true;
-            }
-        }
-        N12Geom g8{};
-        g8.dst_w = r.dst_w; g8.dst_h = r.dst_h; g8.out_w = w.width; g8.cn = r.out_cn;
-        g8.out = w.data; g8.out_step = w.step; g8.packed = 1;
-        if (info)
-            info->kernel = r.out_cn == 3 ? (u8_prog == 0 ? "k4_nv12_resize_u8c3" : (u8_prog == 1 ? "k4_nv12_resize_swap_u8c3" : (canon8 ? "k4_nv12_resize_arith_u8c3" : "k4_nv12_resize_interp_u8c3")))
-                                         : (u8_prog == 0 ? "k4_nv12_resize_u8c4" : (u8_prog == 1 ? "k4_nv12_resize_swap_u8c4" : (canon8 ? "k4_nv12_resize_arith_u8c4" : "k4_nv12_resize_interp_u8c4")));
-        if (dry_run) return 1;
-        const N12Many s8{&ctx, nullptr, 0, nullptr, 0};
-        const bool win8 = r.used != r.batch || !k4_planes_eligible(inline_planes, n_inline, r.dst_w, r.dst_h);
-        const hipError_t e8 = u8_prog == 0   ? launch_n12<ProgNone, uint8_t>(c8, inline_planes, n_inline, g8, s8, win8)
-                              : u8_prog == 1 ? launch_n12<K1Prog<kOpSwapRB>, uint8_t>(c8, inline_planes, n_inline, g8, s8, win8)
-                              : canon8       ? launch_n12<K1CanonProg, uint8_t>(c8, inline_planes, n_inline, g8, s8, win8)
-                                             : launch_n12<InterpProg, uint8_t>(c8, inline_planes, n_inline, g8, s8, win8);
-        return e8 == hipSuccess ? 1 : -(int)e8 - 1000;
-    }
-
-    N12Geom g;
-    g.dst_w = r.dst_w; g.dst_h = r.dst_h; g.out_w = w.width; g.cn = r.out_cn;
-    g.img_stride = w.img_stride; g.ch_stride = w.ch_stride;
-    g.out = w.data; g.out_step = w.step; g.packed = packed ? 1 : 0;
-    g.out2 = w.data2; g.img_stride2 = w.img_stride2; g.ch_stride2 = w.ch_stride2;
-
-    const int swap = r.out_cn == 3 ? (2 | (1 << 2) | (0 << 4)) : (2 | (1 << 2) | (0 << 4) | (3 << 6));
-    const ProgArgs& p = c.prog;
-    const bool fast_prog = planar && p.n == 4 && p.opcode[0] == CVGS_OP_REORDER && p.aux[0] == swap &&
-                           p.opcode[1] == CVGS_OP_MUL && p.opcode[2] == CVGS_OP_SUB && p.opcode[3] == CVGS_OP_DIV;
-    // the same normalisation in the surface's own R, G, B order (cvtColorNV12<COLOR_YUV2RGB_NV12>: no swap)
-    const bool fast_rgb = planar && !f16 && p.n == 3 && p.opcode[0] == CVGS_OP_MUL && p.opcode[1] == CVGS_OP_SUB && p.opcode[2] == CVGS_OP_DIV;
-    ChainArgs c_fd = c;
-    c_fd.prog.fast_div = 0;
-    for (int k = 0; k < 4; ++k) c_fd.prog.rdiv[k] = 0.f;
-    if (fast_prog) fast_div_setup(c_fd.prog, 3, 1, r.out_cn, r.bg);
-    else if (fast_rgb) fast_div_setup(c_fd.prog, 2, 0, r.out_cn, r.bg);
-    // whole surfaces stretched into large targets (cfg #3: 6K -> 1280 x 720): two output pixels per lane (k_nv12_x2.hip) once the
-    // launch is paced by instruction issue rather than by its latency; CVGS_CHAIN_NO_THREAD_FUSION keeps the one-pixel kernel
-    if ((fast_prog || fast_rgb) && !f16 && !segs && r.out_cn == 3 && !(chain_flags & CVGS_CHAIN_NO_THREAD_FUSION)) {
-        const char* x2_env = getenv("CVGS_K4_X2"); // tuning / test hook: 0 = never, 1 = whenever eligible
-        const int64_t wave_rows = (int64_t)r.batch * r.dst_h * ((r.dst_w + 63) / 64);
-        if (x2_env ? x2_env[0] == '1' : wave_rows >= kK4X2MinWaveRows) {
-            const int rc = launch_nv12_x2(c_fd, inline_planes, n_inline, fast_prog, stream, dry_run);
-            if (rc != 0) {
-                if (info) info->kernel = fast_prog ? "k4_nv12_x2_swap_mul_sub_div" : "k4_nv12_x2_mul_sub_div";
-                return rc;
-            }
-        }
-    }
-    // any other chain of the canonical arithmetic shape ([swap] {mul|add|sub} x 0..2 [div] {mul|add|sub} x 0..2): the straight-line K1CanonProg
-    // (k_taps.hpp; round 6 -- a tick of 16 surfaces x 50 crops with one more `add` ran 58 us interpreted against 37 for the compile-time program)
-    bool canon_prog = false;
-    if (!fast_prog && !(fast_rgb && !f16)) { // (planar tensors and packed fp32 / fp16 pixels alike)
-        ProgArgs canon;
-        if (k1_canonicalise(c_fd.prog, r.out_cn, canon)) {
-            c_fd.prog = canon;
-            canon_prog = true;
-        }
-    }
-    if (info)
-        info->kernel = f16 ? (fast_prog ? "k4_nv12_resize_swap_mul_sub_div_f16" : (canon_prog ? "k4_nv12_resize_arith_f16" : "k4_nv12_resize_interp_f16"))
-                           : (fast_prog ? "k4_nv12_resize_swap_mul_sub_div" : (fast_rgb ? "k4_nv12_resize_mul_sub_div" : (canon_prog ? "k4_nv12_resize_arith" : "k4_nv12_resize_interp")));
-    if (info && bf16) info->kernel = bf16_kernel_name(info->kernel);
-    if (dry_run) return 1;
-    const N12Many s{&ctx, segs, n_segs, segs && !r.table ? inline_planes : nullptr, segs && !r.table ? n_inline : 0};
-    // the windowed instantiations: an aspect-ratio window or default-value planes (never for fused chains / staged tables, whose
-    // callers admit stretch geometry only)
-    const bool win = !segs && (r.used != r.batch || !k4_planes_eligible(inline_planes, n_inline, r.dst_w, r.dst_h));
-    hipError_t e;
-    if (bf16) e = k4_launch_bf16(fast_prog ? 0 : (canon_prog ? 1 : 2), c_fd, inline_planes, n_inline, g, s, win);
-    else if (f16) e = fast_prog ? launch_n12<N12SwapMulSubDiv, _Float16>(c_fd, inline_planes, n_inline, g, s, win)
-                           : (canon_prog ? launch_n12<K1CanonProg, _Float16>(c_fd, inline_planes, n_inline, g, s, win)
-                                         : launch_n12<InterpProg, _Float16>(c_fd, inline_planes, n_inline, g, s, win));
-    else if (fast_prog) e = launch_n12<N12SwapMulSubDiv>(c_fd, inline_planes, n_inline, g, s, win);
-    else if (fast_rgb) e = launch_n12<ProgMulSubDiv>(c_fd, inline_planes, n_inline, g, s, win);
-    else e = canon_prog ? launch_n12<K1CanonProg>(c_fd, inline_planes, n_inline, g, s, win) : launch_n12<InterpProg>(c_fd, inline_planes, n_inline, g, s, win);
-    return e == hipSuccess ? 1 : -(int)e - 1000;
+    return k4_pick(c.read.yuv_layout, [&](auto f) { return launch_yuv_family<decltype(f)>(c, inline_planes, n_inline, ctx, dry_run, info, chain_flags); });
 }
 #endif // CVGS_K4_BF16_TU
 

@@ -280,7 +280,7 @@ __global__ __launch_bounds__(64 * kY422Waves) void k_yuv422_resize(const Y422Arg
 
 // the family's traits for the shared launcher (k_yuv_family.hpp)
 hipError_t y422_launch_bf16(int prog, const ChainArgs& c, const PlaneParams* ip, int ni, const YuvFamGeom& g, const YuvFamMany& s, bool win);
-struct Y422Family {
+struct Y422Family : YuvFamDefaults {
     using Geom = Y422Geom;
     template <int NPL, class Prog, typename OT, int RPW, int CN, bool WIN> static const void* kernel() {
         return (const void*)&k_yuv422_resize<NPL, Prog, OT, RPW, CN, WIN>;
@@ -301,7 +301,7 @@ hipError_t y422_launch_bf16(int prog, const ChainArgs& c, const PlaneParams* ip,
     return launch_yuv_fam_bf16<Y422Family>(prog, c, ip, ni, g, s, win);
 }
 #else
-// launch_nv12's contract (it forwards the packed 4:2:2 layouts here): 1 launched / 0 not eligible / < 0 error.  Narrow rows take the
+// 1 launched / 0 not eligible / < 0 error.  Narrow rows take the
 // 4-byte window, so any plane width is served.
 int launch_yuv422(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_inline, LaunchCtx& ctx, bool dry_run, LaunchInfo* info) {
     return launch_yuv_family<Y422Family>(c_in, inline_planes, n_inline, ctx, dry_run, info);

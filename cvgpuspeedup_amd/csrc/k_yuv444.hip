@@ -275,7 +275,7 @@ __global__ __launch_bounds__(64 * kY444Waves) void k_yuv444_resize(const YuvFamA
 
 // the family's traits for the shared launcher (k_yuv_family.hpp)
 hipError_t y444_launch_bf16(int prog, const ChainArgs& c, const PlaneParams* ip, int ni, const YuvFamGeom& g, const YuvFamMany& s, bool win);
-struct Y444Family {
+struct Y444Family : YuvFamDefaults {
     using Geom = YuvFamGeom;
     template <int NPL, class Prog, typename OT, int RPW, int CN, bool WIN> static const void* kernel() {
         return (const void*)&k_yuv444_resize<NPL, Prog, OT, RPW, CN, WIN>;
@@ -294,7 +294,7 @@ hipError_t y444_launch_bf16(int prog, const ChainArgs& c, const PlaneParams* ip,
     return launch_yuv_fam_bf16<Y444Family>(prog, c, ip, ni, g, s, win);
 }
 #else
-// 1 launched / 0 not eligible / < 0 error (launch_nv12's contract).  Rows of one pixel take the 1-byte window, so any plane width is served.
+// 1 launched / 0 not eligible / < 0 error.  Rows of one pixel take the 1-byte window, so any plane width is served.
 int launch_yuv444(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_inline, LaunchCtx& ctx, bool dry_run, LaunchInfo* info) {
     return launch_yuv_family<Y444Family>(c_in, inline_planes, n_inline, ctx, dry_run, info);
 }

@@ -1,14 +1,18 @@
-// k_yuv_family.hpp -- what the YUV resize families with one kernel per layout family share (k_yuv422.hip: packed 4:2:2; k_yuv444.hip:
-// planar 4:4:4): the geometry block of their kernels, the argument-block forms, and ONE host launcher -- launch_nv12's rules (program
-// matching, the u8 cast move, canonicalisation, argument-block selection, rows per wave), written once as a template over a small
-// family-traits type F:
+// k_yuv_family.hpp -- what the YUV resize families with one kernel per layout family share (k_nv12.hip: K4, the 4:2:0 layouts;
+// k_yuv422.hip: packed 4:2:2; k_yuv444.hip: planar 4:4:4): the geometry block of their kernels, the argument-block forms, and ONE host
+// launcher -- the dispatch rules (program matching, the u8 cast move, canonicalisation, argument-block selection, rows per wave), written
+// once as a template over a small family-traits type F:
 //
-//   struct F {
+//   struct F : YuvFamDefaults {
 //       using Geom = ...;                                  // the kernels' second argument: YuvFamGeom or a struct derived from it
 //       template <int NPL, class Prog, typename OT, int RPW, int CN, bool WIN> static const void* kernel();   // the entry points
 //       static bool eligible(const ReadArgs& r);           // is this read the family's?  (kind and layout)
 //       static const char* name(int id);                   // cvgs_kernel_name() of YuvFamName id (CVGS_YUV_FAMILY_NAMES("k_..."))
 //       static hipError_t launch_bf16(int prog, ...);      // the OT = __bf16 instantiations, compiled in the family's bf16 twin file
+//       // what K4 alone redefines (YuvFamDefaults holds the other families' answers):
+//       static constexpr bool kRows4;                      // are there RPW = 4 kernels (fp32, cn 3)?          K4: not for planar chroma
+//       static constexpr bool kManyInline;                 // ... NPL < 0 kernels (fused chains, planes in the arguments)?   K4: likewise
+//       static int frame_kernel(...);                      // another kernel of the family for whole frames (K4: k_nv12_x2.hip); 0: none
 //   };
 //
 // The kernels keep K1's / K4's mapping (lane = output column, wave = RPW output rows of one plane) and differ in how the taps of a source
@@ -69,6 +73,11 @@ enum YuvFamName {
         return n[id];                                                                                                                         \
     }
 
+struct YuvFamDefaults {
+    static constexpr bool kRows4 = true, kManyInline = true;
+    static int frame_kernel(const ChainArgs&, const PlaneParams*, int, bool, bool, const LaunchCtx&, uint32_t, bool, LaunchInfo*) { return 0; }
+};
+
 // the staging buffer of an inline tick's argument block (16 KB / 52 KB): one per thread and size, handed over by address (as K1's / K4's)
 template <int CAP> static KernArgsManyInline<CAP>& yuv_fam_staged() {
     static thread_local std::unique_ptr<KernArgsManyInline<CAP>> staged;
@@ -92,7 +101,7 @@ static hipError_t launch_yuv_fam_r(const ChainArgs& c, const PlaneParams* ip, in
         return hipLaunchKernel(F::template kernel<decltype(npl_tag)::value, Prog, OT, RPW, CN, WIN>(), grid, block, args, 0, s);
     };
     constexpr bool kImage = std::is_same_v<OT, uint8_t>; // packed u8 images: never fused chains, never the 16 KB argument block
-    if constexpr (!kImage && !WIN) if (many.segs && many.planes) {
+    if constexpr (!kImage && !WIN && F::kManyInline) if (many.segs && many.planes) {
         // host descriptors of at most kManyInlineLarge planes: segments + planes in the arguments (16 KB / 52 KB blocks), capturable
         const dim3 grid(col_tiles * row_groups, (unsigned)c.read.batch, (unsigned)many.n_segs);
         auto go = [&](auto cap_tag) {
@@ -141,7 +150,7 @@ static hipError_t launch_yuv_fam_rows(const ChainArgs& c, const PlaneParams* ip,
     if (win) return g.cn == 4 ? launch_yuv_fam_r<F, Prog, OT, 1, 4, true>(c, ip, ni, g, s) : launch_yuv_fam_r<F, Prog, OT, 1, 3, true>(c, ip, ni, g, s);
     // launches in the throughput regime (cvgs_execute_many: the crops of several surfaces; one chain of hundreds of crops): four rows per
     // wave, the rows leaving as 16-byte stores through a wave-private LDS tile -- K4's rule and K4's threshold
-    if constexpr (std::is_same_v<OT, float>) {
+    if constexpr (std::is_same_v<OT, float> && F::kRows4) {
         if (g.cn == 3) {
             int64_t planes = s.segs ? 0 : c.read.batch;
             for (int i = 0; s.segs && i < s.n_segs; ++i) planes += s.segs[i].batch;
@@ -167,11 +176,13 @@ static inline bool yuv_fam_stretch(const PlaneParams* planes, int n, int dst_w, 
     return true;
 }
 
-// Returns 1 if it took the chain, 0 if not eligible, <0 on error (launch_nv12's contract).
+// Returns 1 if it took the chain, 0 if not eligible, <0 on error.
 // ctx.segs (n_segs >= 1): the chains of a cvgs_execute_many launch -- stretch geometry, checked by the caller;
-// c_in.read.batch is the largest batch.  nullptr: one chain (inline_planes).  Any plane width is served.
+// c_in.read.batch is the largest batch.  nullptr: one chain (inline_planes).  Any plane width is served (K4 refuses narrow rows before
+// it comes here).  chain_flags: for F::frame_kernel.
 template <class F>
-static int launch_yuv_family(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_inline, LaunchCtx& ctx, bool dry_run, LaunchInfo* info) {
+static int launch_yuv_family(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_inline, LaunchCtx& ctx, bool dry_run, LaunchInfo* info,
+                             uint32_t chain_flags = 0) {
     const ManySeg* const segs = ctx.segs;
     const int n_segs = ctx.n_segs;
     const ReadArgs& r = c_in.read;
@@ -193,7 +204,7 @@ static int launch_yuv_family(const ChainArgs& c_in, const PlaneParams* inline_pl
     const ChainArgs& c = f16 ? c_cut : c_in;
     if (segs) {
         if (n_segs < 1 || n_segs > CVGS_MAX_CHAINS || c_in.write.data2) return 0;
-        if (!r.table && (!inline_planes || n_inline < 1 || n_inline > kManyInlineLarge)) return 0; // segments without a table: planes in the arguments
+        if (!r.table && (!F::kManyInline || !inline_planes || n_inline < 1 || n_inline > kManyInlineLarge)) return 0; // segments without a table: planes in the arguments
     } else {
         if (r.table || n_inline > kKernargPlanesBig) return 0; // resident tables: generic kernel
         if (n_inline > CVGS_KERNARG_PLANES && !(planar_kind && (c_in.write.depth == CVGS_DEPTH_32F || f16))) return 0; // the large block: tensors only
@@ -272,6 +283,10 @@ static int launch_yuv_family(const ChainArgs& c_in, const PlaneParams* inline_pl
     for (int k = 0; k < 4; ++k) c_fd.prog.rdiv[k] = 0.f;
     if (fast_prog) fast_div_setup(c_fd.prog, 3, 1, r.out_cn, r.bg); // division by the host reciprocal under K1's / K4's guards
     else if (fast_rgb) fast_div_setup(c_fd.prog, 2, 0, r.out_cn, r.bg);
+    if (fast_prog || fast_rgb) { // the two compile-time normalisations at frame size: the family may have another kernel for them
+        const int rc = F::frame_kernel(c_fd, inline_planes, n_inline, fast_prog, f16, ctx, chain_flags, dry_run, info);
+        if (rc != 0) return rc;
+    }
     // any other chain of the canonical arithmetic shape ([swap] {mul|add|sub} x 0..2 [div] {mul|add|sub} x 0..2): the straight-line K1CanonProg
     bool canon_prog = false;
     if (!fast_prog && !(fast_rgb && !f16)) { // (planar tensors and packed fp32 / fp16 pixels alike)

@@ -307,7 +307,7 @@ def test_packed_float_image_outputs(oracle, layout, shape, cn, batch):
     run_both(oracle, build, [surf], shp, np.float32, f, "k4_nv12_resize_arith")  # (multiply: the canonical arithmetic program, round 6)
 
 
-# ---- round 6: the canonical arithmetic program on decoder surfaces (k_taps.hpp: K1CanonProg through launch_n12) ---------------------------------
+# ---- round 6: the canonical arithmetic program on decoder surfaces (k_taps.hpp: K1CanonProg) ---------------------------------
 K4_ARITH = {
     # name: (stages after the read, the kernel it must take)
     "norm_then_add": (lambda f: [cvgs.cvtColor(cvgs.COLOR_RGB2BGR, f), cvgs.multiply(f, [0.3] * 3), cvgs.subtract(f, [1.0, 4.0, 3.2]), cvgs.divide(f, [3.2, 0.6, 11.8]),
@@ -359,3 +359,130 @@ def test_canonical_program_into_a_u8_image(oracle, layout, cn):
 
     ref, name = run_both(oracle, build, [surf], (dst[1], dst[0], cn), np.uint8, u, "k4_nv12_resize_arith_u8c%d" % cn)
     assert name == "k4_nv12_resize_arith_u8c%d" % cn
+
+
+# ---- the launch forms of the shared YUV launcher (k_yuv_family.hpp), for each of K4's three kernel variants -----------------------------
+FORM_LAYOUTS = {"nv12": capi.YUV_NV12, "p010": capi.YUV_P010, "i420": capi.YUV_I420}  # interleaved 8-bit, 16-bit samples, planar chroma
+FW, FH = 64, 36
+
+
+def form_surface(layout, seed):
+    """The bytes of a 64 x 36 surface (P010: 10-bit codes in the high bits of 16-bit samples, as rows of bytes)."""
+    if layout == capi.YUV_P010:
+        return np.ascontiguousarray((H.random_u16((FH + FH // 2, FW), seed) >> 6) << 6).view(np.uint8)
+    if layout in PLANAR:
+        return planar_surface(FW, FH, seed, layout)[0]
+    return H.random_u8((FH * 3 // 2, FW), seed)
+
+
+def form_planes(wrap, surfs, layout, n, whole=False):
+    """n source planes: crops of the surfaces (planar chroma has no crops: the whole surfaces, in turn)."""
+    out = []
+    for i in range(n):
+        m = wrap(surfs[i % len(surfs)])
+        luma = cvgs.GpuMat(FH, FW, cvgs.CV_16UC1 if layout == capi.YUV_P010 else cvgs.CV_8UC1, m.data, m.step, owner=m.owner)
+        out.append(luma if whole or layout in PLANAR else luma.nv12_roi(2 * (i % 13), 2 * (i % 5), 16 + 2 * (i % 11), 8 + 2 * (i % 7)))
+    return out
+
+
+def form_norm(layout, f):
+    scale = 1 / 1023.0 if layout == capi.YUV_P010 else 1 / 255.0
+    return [cvgs.cvtColor(cvgs.COLOR_RGB2BGR, f), cvgs.multiply(f, [scale] * 3), cvgs.subtract(f, [0.485, 0.456, 0.406]), cvgs.divide(f, [0.229, 0.224, 0.225])]
+
+
+# form: (planes, target size, what selects it)
+ONE_CHAIN_FORMS = {
+    "args_8": (8, (16, 8)), "args_64": (9, (16, 8)), "args_320": (65, (16, 8)),  # the planes in the kernel arguments: three block sizes
+    "staged_table": (321, (16, 8)),  # beyond them: the chain's staged table as ONE segment of the fused form
+    # four rows per wave from 32768 wave rows on (fp32, 3 channels; planar chroma keeps one row): 512 planes x 64 rows x one column tile, and one row less
+    "rows4_at_threshold": (512, (64, 64)), "rows4_one_row_less": (512, (64, 63)),
+}
+
+
+@pytest.mark.parametrize("form", sorted(ONE_CHAIN_FORMS))
+@pytest.mark.parametrize("lname", sorted(FORM_LAYOUTS))
+def test_launch_forms_of_one_chain(oracle, lname, form):
+    layout = FORM_LAYOUTS[lname]
+    n, dst = ONE_CHAIN_FORMS[form]
+    surfs = [form_surface(layout, 8400 + i) for i in range(3)]
+    f = cvgs.CV_32FC3
+
+    def build(wrap, out):
+        rd = cvgs.read_nv12(form_planes(wrap, surfs, layout, n), dst, capi.YUV_LIMITED, capi.BT709, False, layout=layout)
+        return [rd] + form_norm(layout, f) + [cvgs.split(f, out, dst)]
+
+    run_both(oracle, build, surfs, (n, 3 * dst[0] * dst[1]), np.float32, cvgs.CV_32FC1, "k4_nv12_resize_swap_mul_sub_div")
+
+
+@pytest.mark.parametrize("window", ["default_planes", "aspect_ratio"])
+@pytest.mark.parametrize("target", ["tensor", "u8_image"])
+@pytest.mark.parametrize("lname", sorted(FORM_LAYOUTS))
+def test_windowed_kernels(oracle, lname, target, window):
+    """used < batch, and an aspect-ratio window: the WIN instantiations of each variant, into a planar tensor and a packed u8 image."""
+    layout = FORM_LAYOUTS[lname]
+    surfs = [form_surface(layout, 8500 + i) for i in range(2)]
+    n, dst = 3, (16, 16)
+    f, u = cvgs.CV_32FC3, cvgs.CV_8UC3
+
+    def build(wrap, out):
+        rd = cvgs.read_nv12(form_planes(wrap, surfs, layout, n, whole=True), dst, capi.YUV_LIMITED, capi.BT601, False, layout=layout)
+        rd.background = cvgs._scalar([114.0, 100.5, 7.25])
+        if window == "default_planes":
+            rd.used_planes = 2
+        else:
+            rd.ar = cvgs.PRESERVE_AR
+        if target == "tensor":
+            return [rd] + form_norm(layout, f) + [cvgs.split(f, out, dst)]
+        return [rd, cvgs.convertTo(f, u, 0.25) if layout == capi.YUV_P010 else cvgs.convertTo(f, u), cvgs.write(u, out, dst)]
+
+    if target == "tensor":
+        run_both(oracle, build, surfs, (n, 3 * dst[0] * dst[1]), np.float32, cvgs.CV_32FC1)
+    else:
+        run_both(oracle, build, surfs, (n, dst[0] * dst[1], 3), np.uint8, u)
+
+
+@pytest.mark.parametrize("dst", [(64, 8), (70, 8)], ids=["full_tile", "ragged_tile"])
+@pytest.mark.parametrize("lname", sorted(FORM_LAYOUTS))
+def test_u8_c3_image_tiles(oracle, lname, dst):
+    """A packed u8 C3 image whose 64-column tile is full (dword stores) and one with a ragged second tile (3 bytes per lane)."""
+    layout = FORM_LAYOUTS[lname]
+    surf = form_surface(layout, 8600)
+    f, u = cvgs.CV_32FC3, cvgs.CV_8UC3
+
+    def build(wrap, out):
+        rd = cvgs.read_nv12(form_planes(wrap, [surf], layout, 1, whole=True)[0], dst, capi.YUV_LIMITED, capi.BT709, False, layout=layout)
+        return [rd, cvgs.convertTo(f, u, 0.25) if layout == capi.YUV_P010 else cvgs.convertTo(f, u), cvgs.write(u, out)]
+
+    run_both(oracle, build, [surf], (dst[1], dst[0], 3), np.uint8, u, "k4_nv12_resize_interp_u8c3" if layout == capi.YUV_P010 else "k4_nv12_resize_u8c3")
+
+
+@pytest.mark.parametrize("per_chain", [5, 129, 513], ids=["256_plane_block", "1024_plane_block", "device_tables"])
+@pytest.mark.parametrize("lname", sorted(FORM_LAYOUTS))
+def test_fused_launch_forms(oracle, lname, per_chain):
+    """Two chains in ONE launch: their planes in the 16 KB argument block (<= 256 planes in all), in the 52 KB block (<= 1024), and beyond that
+    in staged device tables (planar chroma: always tables).  Bit-exact against the oracle."""
+    import torch
+    dev = torch.device("cuda:0")
+    layout = FORM_LAYOUTS[lname]
+    dst = (16, 8)
+    f = cvgs.CV_32FC3
+    surfs = [form_surface(layout, 8700 + i) for i in range(3)]
+    ts = {id(s): torch.from_numpy(s).to(dev) for s in surfs}
+    chains, outs, refs = [], [], []
+    for cam in range(2):
+        def chain(wrap, out):
+            rd = cvgs.read_nv12(form_planes(wrap, surfs[cam:] + surfs[:cam], layout, per_chain), dst, capi.YUV_LIMITED, capi.BT709, False, layout=layout)
+            return [rd] + form_norm(layout, f) + [cvgs.split(f, out, dst)]
+
+        ot = torch.full((per_chain, 3 * dst[0] * dst[1]), -3.0, dtype=torch.float32, device=dev)
+        ref = np.full((per_chain, 3 * dst[0] * dst[1]), -3.0, np.float32)
+        chains.append(chain(lambda a: cvgs.GpuMat.from_tensor(ts[id(a)], cvgs.CV_8UC1), cvgs.GpuMat.from_tensor(ot, cvgs.CV_32FC1)))
+        oracle.execute(cvgs.lower(chain(lambda a: cvgs.GpuMat.from_array(a, cvgs.CV_8UC1), cvgs.GpuMat.from_array(ref, cvgs.CV_32FC1))))
+        outs.append(ot)
+        refs.append(ref)
+    held = cvgs.executeMany(torch.cuda.current_stream(), chains)
+    torch.cuda.synchronize()
+    del held
+    for cam in range(2):
+        assert refs[cam].std() > 0.1
+        H.assert_bit_exact(outs[cam].cpu().numpy(), refs[cam], "fused %s chains of %d planes, chain %d" % (lname, per_chain, cam))

@@ -17,7 +17,9 @@ triple}); each hipv4-amdgcn entry is an ELF whose NT_AMDGPU_METADATA note (type 
 with 'amdhsa.kernels'; the kernel descriptor (<name>.kd in .rodata, 64 bytes) carries the user-SGPR enable bits.
 
 usage: kernel_resources.py [lib.so] [--json out.json] [--check table.json]
+       kernel_resources.py --compare first.so second.so    (which kernels left, came, or changed their machine code: exit 1 if any did)
 """
+import hashlib
 import json
 import os
 import struct
@@ -93,21 +95,26 @@ def _symbols(buf, sections):
     return out
 
 
-def kernels_of(lib_path):
-    """One dict per gfx950 kernel in the library: name, lds, scratch, vgpr, sgpr, dynamic_stack, dispatch_ptr, queue_ptr, kernarg."""
+def _code_objects(lib_path):
+    """Yield (bytes, sections, symbols) of every gfx950 code object in the library."""
     data = open(lib_path, "rb").read()
     fat = next((s for s in _elf_sections(data) if s[0] == ".hip_fatbin"), None)
     if fat is None:
         raise RuntimeError("%s has no .hip_fatbin section" % lib_path)
     fatbin = data[fat[2]:fat[2] + fat[3]]
-    out = []
     for triple, co in _bundles(fatbin):
         if "amdgcn" not in triple or not co.startswith(b"\x7fELF"):
             continue
         if "gfx950" not in triple:
             raise RuntimeError("unexpected device target in %s: %s (the engine is gfx950 only)" % (lib_path, triple))
         secs = _elf_sections(co)
-        syms = _symbols(co, secs)
+        yield co, secs, _symbols(co, secs)
+
+
+def kernels_of(lib_path):
+    """One dict per gfx950 kernel in the library: name, lds, scratch, vgpr, sgpr, dynamic_stack, dispatch_ptr, queue_ptr, kernarg."""
+    out = []
+    for co, secs, syms in _code_objects(lib_path):
         # virtual address -> file offset (descriptors live in .rodata)
         def file_off(va):
             for _n, _t, off, size, addr in secs:
@@ -144,6 +151,26 @@ def kernels_of(lib_path):
                 "preload": preload & 0x7f,           # leading kernel-argument dwords delivered in user SGPRs with the dispatch
             })
     return out
+
+
+def code_hashes(lib_path):
+    """kernel symbol -> sha256 of its bytes in .text (the symbol's value and size): the machine code, and nothing read out of it.
+    (Kernels that call nothing and address no global by relocation -- every kernel of this engine -- are position-independent, so equal
+    code gives equal bytes wherever the linker put it.)"""
+    out = {}
+    for co, secs, syms in _code_objects(lib_path):
+        text = next(s for s in secs if s[0] == ".text")
+        for name, (value, size) in syms.items():
+            if name + ".kd" in syms and text[4] <= value and value + size <= text[4] + text[3]:
+                off = text[2] + (value - text[4])
+                out[name] = hashlib.sha256(co[off:off + size]).hexdigest()
+    return out
+
+
+def compare(first, second):
+    """(only in first, only in second, in both with different bytes): sorted lists of kernel symbols."""
+    a, b = code_hashes(first), code_hashes(second)
+    return sorted(set(a) - set(b)), sorted(set(b) - set(a)), sorted(n for n in a if n in b and a[n] != b[n])
 
 
 def demangle(names):
@@ -190,6 +217,14 @@ def drift(kernels, table, vgpr_slack=4):
 
 
 def main(argv):
+    if len(argv) == 4 and argv[1] == "--compare":
+        gone, came, differ = compare(argv[2], argv[3])
+        for title, names in (("only in the first", gone), ("only in the second", came), ("bytes differ", differ)):
+            for n in demangle(names):
+                print("  %s: %s" % (title, n[:200]))
+        print("%d kernels in both, %d only in %s, %d only in %s, %d whose bytes differ" % (
+            len(code_hashes(argv[2])) - len(gone), len(gone), os.path.basename(argv[2]), len(came), os.path.basename(argv[3]), len(differ)))
+        return 1 if gone or came or differ else 0
     lib = DEFAULT_LIB
     out_json = check = None
     i = 1

@@ -103,6 +103,17 @@ class ChainDesc(C.Structure):
                 ("reserved", C.c_int32), ("ops", Op * MAX_OPS), ("write", WriteDesc)]
 
 
+# device-built plane tables (include/cvgs_hip_ext.h: cvgs_plane_tables_from_boxes)
+BOX_XYXY_F32, BOX_XYWH_I32 = 0, 1
+
+
+class BoxTableDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("frame", Image2D), ("read_kind", C.c_int32),
+                ("src_type", C.c_int32), ("yuv_layout", C.c_int32), ("dst_width", C.c_int32), ("dst_height", C.c_int32),
+                ("aspect_ratio", C.c_int32), ("box_format", C.c_int32), ("max_boxes", C.c_int32), ("boxes", C.c_void_p),
+                ("count", C.c_void_p), ("table_out", C.c_void_p), ("rects_out", C.c_void_p)]
+
+
 # every symbol include/cvgs_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("cvgs_abi_version", C.c_int, []),
@@ -140,6 +151,7 @@ SYMBOLS = [
     ("cvgs_queue_stream", C.c_void_p, [C.c_void_p]),
     ("cvgs_queue_profile", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("cvgs_queue_destroy", C.c_int, [C.c_void_p]),
+    ("cvgs_plane_tables_from_boxes", C.c_int, [C.POINTER(BoxTableDesc), C.c_int32, C.c_void_p]),
     ("cvgs_range_push", None, [C.c_char_p]),
     ("cvgs_range_pop", None, []),
 ]

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "cvgs_device.h"
+#include "cvgs_geometry.h"
 
 using namespace cvgs;
 
@@ -73,34 +74,7 @@ bool is_yuv422(int layout) { return layout == CVGS_YUV_YUYV || layout == CVGS_YU
 bool is_yuv444(int layout) { return layout == CVGS_YUV_I444; } // planar 4:4:4: three full-resolution planes, uv_offset apart
 bool is_warp(int kind) { return kind == CVGS_READ_WARP_AFFINE || kind == CVGS_READ_WARP_PERSPECTIVE; }
 
-// Host half of fk::Resize::build: the kernel-side scale factors and the aspect-ratio window.
-// IGNORE_AR follows cv::cuda::resize's host code (scale = float(1.0 / (double(dst)/src))).
-// PRESERVE_AR* fits the source inside the target keeping its aspect ratio (scale by height, fall
-// back to width), centred (or left-aligned), extent rounded to nearest (RN_EVEN: down to even).
-void plane_geometry(int sw, int sh, int dw, int dh, int ar, PlaneParams& P) {
-    int tw = dw, th = dh, x0 = 0, y0 = 0;
-    if (ar != CVGS_IGNORE_AR) {
-        float s = (float)dh / (float)sh;
-        tw = (int)std::round(s * (float)sw);
-        if (ar == CVGS_PRESERVE_AR_RN_EVEN) tw -= tw % 2;
-        if (tw > dw) {
-            s = (float)dw / (float)sw;
-            tw = dw;
-            th = (int)std::round(s * (float)sh);
-            if (ar == CVGS_PRESERVE_AR_RN_EVEN) th -= th % 2;
-        }
-        tw = tw < 1 ? 1 : tw;
-        th = th < 1 ? 1 : th;
-        x0 = ar == CVGS_PRESERVE_AR_LEFT ? 0 : (dw - tw) / 2;
-        y0 = (dh - th) / 2;
-    }
-    P.fx = (float)(1.0 / ((double)tw / (double)sw));
-    P.fy = (float)(1.0 / ((double)th / (double)sh));
-    P.x1 = x0;
-    P.y1 = y0;
-    P.x2 = x0 + tw - 1;
-    P.y2 = y0 + th - 1;
-}
+// plane_geometry (host half of fk::Resize::build: the scale factors and the aspect-ratio window): cvgs_geometry.h, shared with k_boxes.hip
 
 // Host descriptors of one call: inline storage for everything that fits the kernel-argument block (so that a call with
 // <= CVGS_KERNARG_PLANES planes never touches the heap), heap beyond that.
@@ -1437,6 +1411,76 @@ int cvgs_plane_table_hull(const cvgs_read_desc* read, const void** lo, const voi
     if (!hull.lo) return fail(CVGS_ERR_INVALID, "plane_table_hull: used_planes < 1");
     *lo = hull.lo;
     *hi = hull.hi;
+    return CVGS_OK;
+}
+
+// Device plane tables from device-side boxes (include/cvgs_hip_ext.h).  Everything is validated here, on the host, before the first HIP
+// call; the kernel (k_boxes.hip) clamps every box into the frame described here, so the checks below bound what the table's planes read.
+int cvgs_plane_tables_from_boxes(const cvgs_box_table_desc* descs, int32_t n, cvgs_stream_t stream) {
+    if (!descs) return fail(CVGS_ERR_INVALID, "plane_tables_from_boxes: null descriptors");
+    if (n < 1 || n > CVGS_MAX_CHAINS) return fail(CVGS_ERR_INVALID, "plane_tables_from_boxes: n must be in [1, CVGS_MAX_CHAINS]");
+    BoxFrame frames[CVGS_MAX_CHAINS];
+    for (int i = 0; i < n; ++i) {
+        const cvgs_box_table_desc& d = descs[i];
+        if (d.struct_size != sizeof(cvgs_box_table_desc)) return fail(CVGS_ERR_INVALID, "cvgs_box_table_desc size mismatch (ABI)");
+        if (d.flags) return fail(CVGS_ERR_INVALID, "plane_tables_from_boxes: flags must be 0");
+        if (d.read_kind < CVGS_READ_PIXEL || d.read_kind > CVGS_READ_WARP_PERSPECTIVE) return fail(CVGS_ERR_INVALID, "bad read kind");
+        if (is_warp(d.read_kind)) return fail(CVGS_ERR_UNSUPPORTED, "plane_tables_from_boxes: warp reads (WARP_AFFINE / WARP_PERSPECTIVE) take host descriptors");
+        if (!is_resize(d.read_kind))
+            return fail(CVGS_ERR_UNSUPPORTED, "plane_tables_from_boxes: per-pixel reads (READ_PIXEL / READ_NV12) are not served, boxes feed the resize kinds");
+        const bool yuv = is_nv12(d.read_kind);
+        if (yuv) {
+            if (d.yuv_layout < CVGS_YUV_NV12 || d.yuv_layout > CVGS_YUV_I444) return fail(CVGS_ERR_INVALID, "bad yuv_layout");
+            if (d.yuv_layout != CVGS_YUV_NV12 && d.yuv_layout != CVGS_YUV_NV21)
+                return fail(CVGS_ERR_UNSUPPORTED, "plane_tables_from_boxes: device plane tables serve the NV12 / NV21 layouts only (P010 / I420 / YV12 / YUYV / UYVY / I444: host descriptors)");
+            if (d.src_type != CVGS_MAKETYPE(CVGS_DEPTH_8U, 1)) return fail(CVGS_ERR_INVALID, "NV12 reads need a CV_8UC1 source");
+        }
+        if (d.max_boxes < 1 || d.max_boxes > 65535) return fail(CVGS_ERR_INVALID, "max_boxes must be in [1, 65535]");
+        if (d.box_format != CVGS_BOX_XYXY_F32 && d.box_format != CVGS_BOX_XYWH_I32) return fail(CVGS_ERR_INVALID, "bad box format");
+        if (!d.boxes) return fail(CVGS_ERR_INVALID, "plane_tables_from_boxes: boxes is null");
+        if (!d.table_out) return fail(CVGS_ERR_INVALID, "plane_tables_from_boxes: table_out is null");
+        if (((uintptr_t)d.table_out & 7) || (((uintptr_t)d.boxes | (uintptr_t)d.count | (uintptr_t)d.rects_out) & 3))
+            return fail(CVGS_ERR_INVALID, "plane_tables_from_boxes: table_out needs 8-byte, boxes / count / rects_out 4-byte alignment");
+        if (d.dst_width < 1 || d.dst_height < 1) return fail(CVGS_ERR_INVALID, "resize target must be positive");
+        if (d.dst_width > kMaxDim || d.dst_height > kMaxDim) return fail(CVGS_ERR_UNSUPPORTED, "resize target wider or taller than 2^24 pixels");
+        if (d.aspect_ratio < CVGS_PRESERVE_AR || d.aspect_ratio > CVGS_PRESERVE_AR_LEFT) return fail(CVGS_ERR_INVALID, "bad aspect ratio mode");
+        // the frame, as lower() checks a host-described plane
+        const cvgs_image2d& im = d.frame;
+        const int esz = depth_bytes(type_depth(d.src_type)) * CVGS_TYPE_CN(d.src_type);
+        if (CVGS_TYPE_CN(d.src_type) > 4 || esz < 1) return fail(CVGS_ERR_INVALID, "bad source type");
+        if (!im.data || im.width < 1 || im.height < 1) return fail(CVGS_ERR_INVALID, "empty source plane");
+        if (im.width > kMaxDim || im.height > kMaxDim) return fail(CVGS_ERR_UNSUPPORTED, "source plane wider or taller than 2^24 pixels");
+        if ((int64_t)im.step < (int64_t)im.width * esz) return fail(CVGS_ERR_INVALID, "source step smaller than a row");
+        // the aspect-ratio fit rounds dst_height / h * w (and dst_width / w * h) to an int: keep every box of the frame inside its range
+        if ((int64_t)d.dst_height * im.width > ((int64_t)1 << 30) || (int64_t)d.dst_width * im.height > ((int64_t)1 << 30))
+            return fail(CVGS_ERR_UNSUPPORTED, "plane_tables_from_boxes: dst_height * frame width or dst_width * frame height beyond 2^30");
+        int64_t uv_off = 0;
+        if (yuv) {
+            if ((im.width & 1) || (im.height & 1)) return fail(CVGS_ERR_INVALID, "NV12 planes need even dimensions");
+            if (im.uv_offset < 0 || (im.uv_offset & 1)) return fail(CVGS_ERR_INVALID, "NV12 uv_offset must be even and non-negative");
+            if (im.step & 1) return fail(CVGS_ERR_INVALID, "plane_tables_from_boxes: NV12 frames need an even step (the chroma offset of a crop at row t is uv_offset - (t/2)*step and must be even)");
+            uv_off = im.uv_offset ? (int64_t)im.uv_offset : (int64_t)im.height * im.step;
+            if (uv_off > INT32_MAX) return fail(CVGS_ERR_UNSUPPORTED, "4:2:0 surfaces whose luma plane exceeds 2 GiB");
+            if (uv_off < (int64_t)(im.height / 2) * im.step) return fail(CVGS_ERR_INVALID, "plane_tables_from_boxes: NV12 uv_offset lies inside the luma rows");
+        } else if (im.uv_offset) {
+            return fail(CVGS_ERR_INVALID, "plane_tables_from_boxes: uv_offset belongs to the NV12 kinds");
+        }
+        BoxFrame& f = frames[i];
+        f = BoxFrame{};
+        f.data = (const uint8_t*)im.data;
+        f.boxes = d.boxes;
+        f.count = d.count;
+        f.table = (PlaneParams*)d.table_out;
+        f.rects = d.rects_out;
+        f.w = im.width; f.h = im.height; f.step = im.step;
+        f.uv_off = (int32_t)uv_off;
+        f.esz = esz;
+        f.yuv420 = yuv ? 1 : 0;
+        f.dst_w = d.dst_width; f.dst_h = d.dst_height; f.ar = d.aspect_ratio;
+        f.fmt = d.box_format; f.max_boxes = d.max_boxes;
+    }
+    const int e = launch_boxes(frames, n, stream);
+    if (e) return hip_fail((hipError_t)e, "plane_tables_from_boxes: kernel launch");
     return CVGS_OK;
 }
 

@@ -21,8 +21,9 @@ static constexpr int kDepthBF16 = 8;
 // returned pointer lives as long as the library).  Implemented in cvgs_api.cpp.
 const char* bf16_kernel_name(const char* f16_name);
 
-// Per-plane read parameters, precomputed on the host in double precision so that the device never
-// re-derives a scale factor (bit-exactness of fx/fy is part of the parity contract).
+// Per-plane read parameters, precomputed in double precision ONCE per plane so that no resize kernel
+// re-derives a scale factor (bit-exactness of fx/fy is part of the parity contract): on the host by the
+// lowering, or on the device by the table builder (k_boxes.hip) -- one text for both, cvgs_geometry.h.
 struct PlaneParams {        // 48 bytes
     const uint8_t* data;    // pixel (0,0) of the crop / image
     int32_t w, h;           // source extent in pixels (NV12: luma extent)
@@ -281,6 +282,26 @@ int launch_circular_push(const ChainArgs& c, const PlaneParams& plane, const Cop
                          uint32_t chain_flags, void* stream, const CircDev* dev = nullptr);
 int launch_circular_bump(const uint64_t* count, void* stream);
 
+
+// ---- device-built plane tables (k_boxes.hip): one frame's part of a cvgs_plane_tables_from_boxes launch, 96 bytes --------------
+struct BoxFrame {
+    const uint8_t* data;     // the whole frame
+    const void* boxes;       // max_boxes x 4 floats / int32
+    const int32_t* count;    // live boxes, or nullptr = max_boxes
+    PlaneParams* table;      // out: PlaneParams[max_boxes]
+    int32_t* rects;          // out: int32[max_boxes][4], or nullptr
+    int32_t w, h, step;
+    int32_t uv_off;          // 4:2:0 frames: bytes from data to the chroma of luma row 0 (resolved: never 0); pixel frames: 0
+    int32_t esz;             // bytes per pixel
+    int32_t yuv420;          // 1: snap boxes to even coordinates
+    int32_t dst_w, dst_h, ar;
+    int32_t fmt, max_boxes;  // cvgs_box_format
+    int32_t pad[3];
+};
+static_assert(sizeof(BoxFrame) == 96, "BoxFrame layout");
+static constexpr int kBoxFramesSmall = 16; // a tick of 16 cameras: a 1.5 KB argument block; more frames: the 12 KB one
+// validated by the caller; frames[0..n), n <= CVGS_MAX_CHAINS.  0 or a HIP error code
+int launch_boxes(const BoxFrame* frames, int n, void* stream);
 
 // ---- device-side arrival flags of the P2P fused-write exchange (k_exchange.hip) ----------------------------------------------
 #define CVGS_MAX_EXCHANGE_PEERS 16

@@ -694,6 +694,56 @@ def build_plane_table(read_iop):
     return bytes(buf)
 
 
+# ---- device-built plane tables: crops from a detector's device-side boxes (include/cvgs_hip_ext.h) --------------------------
+BOX_XYXY_F32, BOX_XYWH_I32 = capi.BOX_XYXY_F32, capi.BOX_XYWH_I32
+
+
+def _dev_ptr(x):
+    """A device address from a torch tensor, an int, or None (0)."""
+    if x is None:
+        return 0
+    return int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
+
+
+def box_table_desc(frame, boxes, table, max_boxes, dsize, ar=IGNORE_AR, box_format=BOX_XYXY_F32, count=None, rects=None,
+                   kind=capi.READ_RESIZE_LINEAR, layout=capi.YUV_NV12):
+    """One cvgs_box_table_desc: `frame` is the GpuMat of the WHOLE frame (an NV12 / NV21 luma view for kind READ_NV12_RESIZE_LINEAR);
+    boxes / count / table / rects are device buffers (torch tensors or raw pointers): max_boxes x 4 float32 (XYXY) or int32 (XYWH), one
+    int32 or None, 48 * max_boxes bytes, max_boxes x 4 int32 or None."""
+    d = capi.BoxTableDesc()
+    d.struct_size = C.sizeof(capi.BoxTableDesc)
+    d.frame = frame.image2d()
+    d.read_kind, d.src_type, d.yuv_layout = kind, frame.cv_type, layout if kind == capi.READ_NV12_RESIZE_LINEAR else 0
+    d.dst_width, d.dst_height, d.aspect_ratio = int(dsize[0]), int(dsize[1]), ar
+    d.box_format, d.max_boxes = box_format, int(max_boxes)
+    d.boxes, d.count, d.table_out, d.rects_out = _dev_ptr(boxes) or None, _dev_ptr(count) or None, _dev_ptr(table) or None, _dev_ptr(rects) or None
+    return d
+
+
+def plane_tables_from_boxes(stream, descs):
+    """cvgs_plane_tables_from_boxes: ONE small kernel on `stream` writes the device plane tables of every desc (box_table_desc) from the
+    boxes in device memory; nothing is copied to the host, nothing synchronises, and the launch can be captured."""
+    lib = capi.load_library()
+    descs = list(descs)
+    arr = (capi.BoxTableDesc * len(descs))(*descs)
+    capi.check(lib.cvgs_plane_tables_from_boxes(arr, len(descs), stream_handle(stream)))
+
+
+def resize_boxes(frame, table, max_boxes, dsize, background=None, ar=IGNORE_AR, yuv=None, layout=capi.YUV_NV12):
+    """The batched read "resize from a device-built table of `frame`": batch = used_planes = max_boxes (validity is per plane, inside the
+    table), and the chain states the whole frame's byte range (cvgs_plane_table_hull of the one whole-frame view) for the independence
+    check of cvgs_execute_many.  yuv = (range, primaries, alpha) makes it the NV12 / NV21 read of a decoder surface."""
+    kind = capi.READ_NV12_RESIZE_LINEAR if yuv is not None else capi.READ_RESIZE_LINEAR
+    whole = ReadIOp(kind, frame.cv_type, [frame], 1, (int(dsize[0]), int(dsize[1])), ar, background, yuv)
+    whole.yuv_layout = layout if yuv is not None else 0
+    rd = ReadIOp(kind, frame.cv_type, None, int(max_boxes), (int(dsize[0]), int(dsize[1])), ar, background, yuv, table=_dev_ptr(table),
+                 batch=int(max_boxes))
+    rd.yuv_layout = whole.yuv_layout
+    rd.table_hull = table_hull(whole)
+    rd.frame = frame  # (keeps the frame's storage alive with the IOp)
+    return rd
+
+
 class CircularTensor:
     """cvGS::CircularTensor<I, O, COLOR_PLANES, BATCH, ORDER, CP_MODE> (reference include/cvGPUSpeedup.cuh:600-627)."""
 

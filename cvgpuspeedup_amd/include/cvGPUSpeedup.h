@@ -560,6 +560,104 @@ public:
     CUDA_T(O)* data() { return this->ptr_a.data; }
 };
 
+// ---- crops from a detector's device-side boxes (engine extension: cvgs_plane_tables_from_boxes, include/cvgs_hip_ext.h) ----------
+// The second stage of a detection pipeline without the host in the loop: the boxes a network has just written on this GPU become a
+// device plane table in ONE small kernel on the stream, and resize<T, INTER_LINEAR, AR>(deviceCrops, bg) reads that table like any other
+// batched resize -- executeOperations, ChainBatch, recordTicks, graph capture.  update() copies nothing to the host and never synchronises.
+//   cvGS::DeviceCrops crops(50);                                          // owns the table (and the rectangle buffer) of up to 50 boxes
+//   crops.update(stream, frame, d_boxes, d_count, CVGS_BOX_XYXY_F32, cv::Size(64, 128));
+//   cvGS::executeOperations(stream, cvGS::resize<CV_8UC3, cv::INTER_LINEAR>(crops), ..., cvGS::split<CV_32FC3>(tensor, cv::Size(64, 128)));
+// Boxes are clamped into the frame; invalid boxes (NaN, empty, outside, at or beyond *d_count) give planes of the background value;
+// rects() (device int32[maxBoxes][4]: x, y, w, h; zeros for an invalid box) maps results back to frame coordinates.
+class DeviceCrops {
+public:
+    explicit DeviceCrops(int maxBoxes, bool withRects = true) : max_(maxBoxes) {
+        if (maxBoxes < 1 || maxBoxes > 65535) throw std::runtime_error("cvGS::DeviceCrops: maxBoxes must be in [1, 65535]");
+        void* p = nullptr;
+        fk::hip_check(hipMalloc(&p, cvgs_plane_table_bytes(maxBoxes)), "hipMalloc(plane table)");
+        table_ = std::shared_ptr<void>(p, [](void* q) { (void)hipFree(q); });
+        if (withRects) {
+            fk::hip_check(hipMalloc(&p, (size_t)maxBoxes * 4 * sizeof(int32_t)), "hipMalloc(rects)");
+            rects_ = std::shared_ptr<void>(p, [](void* q) { (void)hipFree(q); });
+        }
+    }
+    // enqueue the builder for ONE frame: `boxes` = device, maxBoxes x 4 floats (CVGS_BOX_XYXY_F32) or int32 (CVGS_BOX_XYWH_I32); `count` =
+    // device int32 or nullptr (= maxBoxes).  The frame's type is taken from the GpuMat; dsize / ar must be those of the resize that reads it.
+    void update(const cv::cuda::Stream& stream, const cv::cuda::GpuMat& frame, const void* boxes, const int32_t* count, cvgs_box_format format,
+                const cv::Size& dsize, AspectRatio ar = IGNORE_AR) {
+        const cvgs_box_table_desc d = describe(frame, boxes, count, format, dsize, ar);
+        fk::detail::check_status(cvgs_plane_tables_from_boxes(&d, 1, cv::cuda::StreamAccessor::getStream(stream)));
+    }
+    // one frame's part of a several-camera update
+    struct Job {
+        DeviceCrops* crops;
+        cv::cuda::GpuMat frame;
+        const void* boxes;
+        const int32_t* count;
+    };
+    // several DeviceCrops (the cameras of a tick) in ONE launch
+    static void update(const cv::cuda::Stream& stream, const std::vector<Job>& jobs, cvgs_box_format format, const cv::Size& dsize,
+                       AspectRatio ar = IGNORE_AR) {
+        std::vector<cvgs_box_table_desc> d;
+        d.reserve(jobs.size());
+        for (const Job& j : jobs) {
+            if (!j.crops) throw std::runtime_error("cvGS::DeviceCrops::update: null DeviceCrops");
+            d.push_back(j.crops->describe(j.frame, j.boxes, j.count, format, dsize, ar));
+        }
+        fk::detail::check_status(cvgs_plane_tables_from_boxes(d.data(), (int32_t)d.size(), cv::cuda::StreamAccessor::getStream(stream)));
+    }
+    int maxBoxes() const { return max_; }
+    const void* table() const { return table_.get(); }
+    const int32_t* rects() const { return static_cast<const int32_t*>(rects_.get()); } // nullptr when built without
+    // what the last update() described (the read built from it must agree)
+    const cv::cuda::GpuMat& frame() const { return frame_; }
+    cv::Size dsize() const { return dsize_; }
+    AspectRatio aspectRatio() const { return ar_; }
+private:
+    cvgs_box_table_desc describe(const cv::cuda::GpuMat& frame, const void* boxes, const int32_t* count, cvgs_box_format format, const cv::Size& dsize,
+                                 AspectRatio ar) {
+        cvgs_box_table_desc d;
+        std::memset(&d, 0, sizeof(d));
+        d.struct_size = sizeof(d);
+        d.frame = cvgs_image2d{frame.data, frame.cols, frame.rows, (int32_t)frame.step, 0};
+        d.read_kind = CVGS_READ_RESIZE_LINEAR;
+        d.src_type = frame.type();
+        d.dst_width = dsize.width; d.dst_height = dsize.height; d.aspect_ratio = (int)ar;
+        d.box_format = (int32_t)format; d.max_boxes = max_;
+        d.boxes = boxes; d.count = count;
+        d.table_out = table_.get(); d.rects_out = static_cast<int32_t*>(rects_.get());
+        frame_ = frame; dsize_ = dsize; ar_ = ar;
+        return d;
+    }
+    int max_;
+    std::shared_ptr<void> table_, rects_;
+    cv::cuda::GpuMat frame_;
+    cv::Size dsize_;
+    AspectRatio ar_ = IGNORE_AR;
+};
+
+// resize<T, INTER_LINEAR, AR>(deviceCrops, backgroundValue): the batched read over the device-built table -- maxBoxes planes of the size and
+// aspect-ratio mode of the last update() (AR must be that mode), invalid boxes and the AR padding take backgroundValue.  fk::executeDivergentBatch
+// keeps refusing device tables (it selects planes on the host).
+template <int T, int INTER_F, AspectRatio AR_ = IGNORE_AR>
+inline auto resize(const DeviceCrops& crops, const cv::Scalar& backgroundValue_ = cvScalar_set<CV_MAKETYPE(CV_32F, CV_MAT_CN(T))>(0)) {
+    static_assert(isSupportedInterpolation<INTER_F>, "Interpolation type not supported yet.");
+    const cv::cuda::GpuMat& f = crops.frame();
+    if (!f.data) throw std::runtime_error("cvGS::resize(DeviceCrops): update() has not described a frame yet");
+    if (f.type() != T) throw std::runtime_error("cvGS::resize(DeviceCrops): the frame of the last update() is not of type T");
+    if (crops.aspectRatio() != AR_) throw std::runtime_error("cvGS::resize(DeviceCrops): AR differs from the mode the table was built with");
+    fk::DeviceTableResizeRead<CUDA_T(T)> rd;
+    rd.table = crops.table();
+    rd.batch = crops.maxBoxes();
+    rd.dsize = fk::Size(crops.dsize().width, crops.dsize().height);
+    rd.ar = (int)AR_;
+    for (int c = 0; c < CV_MAT_CN(T); ++c) rd.background[c] = static_cast<float>(backgroundValue_[c]);
+    // the whole frame's byte range: cvgs_plane_table_hull of the one whole-frame view
+    rd.src_lo = f.data;
+    rd.src_hi = (const unsigned char*)f.data + (size_t)f.step * (size_t)(f.rows - 1) + (size_t)f.cols * f.elemSize();
+    return rd;
+}
+
 // ---- launch batching (engine extension, see fk::ChainBatch): several independent chains, ONE kernel launch -------------
 class ChainBatch {
 public:

@@ -289,6 +289,7 @@ template <size_t N> struct BatchCropSpec { std::array<Rect, N> rects; };
 template <InterpolationType IT> struct IncompleteResize { Size dsize; };
 template <typename T> struct ResizeRead;
 template <typename T> struct BatchResizeRead;
+template <typename T> struct DeviceTableResizeRead;
 template <typename T> struct BatchPixelRead;
 template <ND D, typename T> struct PerThreadRead;
 
@@ -637,6 +638,30 @@ template <typename T> struct BatchResizeRead {
     }
 };
 
+// The batched resize over a DEVICE plane table that cvgs_plane_tables_from_boxes wrote from a detector's device-side boxes (cvGS::DeviceCrops):
+// batch = used_planes = the table's entries (validity is per plane, inside the table), and the chain states the whole frame's byte range
+// for the independence check of cvgs_execute_many (ChainBatch, recordTicks).
+template <typename T> struct DeviceTableResizeRead {
+    const void* table = nullptr;
+    int batch = 0;
+    Size dsize;
+    int ar = CVGS_IGNORE_AR;
+    float background[4] = {0, 0, 0, 0};
+    const void* src_lo = nullptr;
+    const void* src_hi = nullptr;
+    using OutputType = VectorType_t<float, cn<T>>;
+    static constexpr Stage stage = Stage::Read;
+    void lower(ChainBuilder& b) const {
+        cvgs_read_desc& r = b.d.read;
+        r.kind = CVGS_READ_RESIZE_LINEAR; r.src_type = cvGS::cv_type_of<T>;
+        r.batch = batch; r.used_planes = batch;
+        r.src = table; r.flags = CVGS_READ_FLAG_TABLE_ON_DEVICE;
+        r.table_src_lo = src_lo; r.table_src_hi = src_hi;
+        r.dst_width = dsize.width; r.dst_height = dsize.height; r.aspect_ratio = ar;
+        for (int i = 0; i < 4; ++i) r.background[i] = background[i];
+    }
+};
+
 // N pitched sources read per pixel (the batch executeOperations overloads)
 template <typename T> struct BatchPixelRead {
     detail::SmallVec<cvgs_image2d, detail::kInlinePlanes> planes;
@@ -773,6 +798,7 @@ namespace detail {
 template <typename R> struct resize_source { using type = void; };
 template <typename T> struct resize_source<ResizeRead<T>> { using type = T; };
 template <typename T> struct resize_source<BatchResizeRead<T>> { using type = T; };
+template <typename T> struct resize_source<DeviceTableResizeRead<T>> { using type = T; };
 template <typename A, typename B> struct redundant_cast : std::false_type {};
 template <typename A, typename I, typename O> struct redundant_cast<A, Unary<SaturateCast<I, O>>>
     : std::bool_constant<!std::is_void_v<typename resize_source<A>::type> && std::is_same_v<typename resize_source<A>::type, I> &&

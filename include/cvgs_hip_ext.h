@@ -1,7 +1,8 @@
 /*
  * cvgs_hip_ext.h -- ENGINE EXTENSIONS of libcvgs_hip.so that have no counterpart in the reference's interface: the device-side
- * descriptor queue (cvgs_queue_*: an opt-in submission path, frozen since round 5) and the device-side arrival flags of the sharded
- * batched-crop path (cvgs_exchange_*: BASELINE cfg #5, SURVEY.md 8e option 2).  The drop-in boundary -- what replaces
+ * descriptor queue (cvgs_queue_*: an opt-in submission path, frozen since round 5), the device-side arrival flags of the sharded
+ * batched-crop path (cvgs_exchange_*: BASELINE cfg #5, SURVEY.md 8e option 2) and plane tables built on the device from a detector's
+ * device-side boxes (cvgs_plane_tables_from_boxes).  The drop-in boundary -- what replaces
  * fk::executeOperations and fk::CircularTensor (reference include/cvGPUSpeedup.cuh:464-627) -- is include/cvgs_hip.h alone; nothing
  * there depends on this file.  Same conventions: plain C, asynchronous on the given stream, 0 or a negative cvgs_status.
  */
@@ -145,6 +146,58 @@ int cvgs_exchange_wait(const void* const* own_flag_words, int32_t n, uint64_t va
  * enqueued.  About one kernel boundary (~2 us) per step, against >= 20 us of link time per step on 8 GPUs.                      */
 int cvgs_exchange_step(void* const* peer_flag_words, const void* const* own_flag_words, int32_t n, uint64_t* step_counter, uint64_t lag,
                        double timeout_ms, void* err_words, cvgs_stream_t stream);
+
+/* ---- device-built plane tables: crops from a detector's device-side boxes ------------------------------------------------------
+ * The second stage of a detection pipeline reads boxes that a network has just written on the same GPU.  Every other way to describe a
+ * crop (cvgs_image2d arrays, cvgs_plane_table_build) goes through the host: copy the boxes back, synchronise, build, launch again.
+ * cvgs_plane_tables_from_boxes enqueues ONE small kernel on `stream` that writes the device plane tables of up to CVGS_MAX_CHAINS
+ * frames from boxes in device memory (grid y = frame, one work-item per box; the n descriptors travel in the kernel arguments).
+ * Nothing is allocated, staged or synchronised, and the launch can be captured into a HIP graph between the producer of the boxes and
+ * the chains that read the tables.  Its cost has not been timed.
+ *
+ * Boxes are clamped into the frame; `xb / yb` of CVGS_BOX_XYXY_F32 are exclusive edges in pixel coordinates:
+ *   XYXY_F32  four floats (xa, ya, xb, yb): l = (int)floorf(fminf(fmaxf(xa, 0), W)), r = (int)ceilf(fminf(fmaxf(xb, 0), W)), t / b the
+ *             same with H.  The clamp comes first, so +-inf and values beyond the int range are fine; a NaN in any slot makes the box invalid.
+ *   XYWH_I32  four int32 (x, y, w, h): l = clamp(x, 0, W), r = clamp((int64)x + w, 0, W), t / b the same; w <= 0 or h <= 0: invalid.
+ * 4:2:0 frames (CVGS_READ_NV12_RESIZE_LINEAR, NV12 / NV21): l and t are then rounded DOWN to even, r and b UP to even and clamped again, so
+ * that every view is one the host lowering accepts (even origin, even size).  The frame's width, height and step must be even.
+ * A box is VALID iff r > l && b > t after that.  `count` (device int32, or NULL = max_boxes) is clamped to [0, max_boxes]; entries at or
+ * beyond it are invalid boxes.
+ *   valid box    table_out[i] = exactly what cvgs_plane_table_build writes for the view data = frame.data + t*step + l*elemSize, width =
+ *                r - l, height = b - t, step = the frame's (4:2:0: uv_offset = frame's chroma offset + (t/2)*step + l - (t*step + l)),
+ *                with dst_width / dst_height / aspect_ratio: the same bytes (scale factors included: same fp32 / fp64 operations, same
+ *                source text on both sides).
+ *   invalid box  a plane that yields the chain's background value in every pixel and reads only bytes of the frame: the frame's own
+ *                data / width / height / step (4:2:0: its chroma offset, uv_offset or height * step), fx = fy = 1, and the EMPTY
+ *                destination window x1 = y1 = 0, x2 = y2 = -1 -- every kernel that takes a device table sends pixels outside the
+ *                window through the background path, as it does for aspect-ratio padding.
+ *   rects_out    optional, device int32[max_boxes][4]: (l, t, r - l, b - t) of a valid box, (0, 0, 0, 0) of an invalid one -- maps the
+ *                consumer's results back to frame coordinates.
+ * USING THE TABLE: a chain passes table_out as read.src with CVGS_READ_FLAG_TABLE_ON_DEVICE, batch = used_planes = max_boxes (validity is
+ * per plane, inside the table; used_planes only describes a tail), the same kind / src_type / yuv_layout / dst size / aspect ratio.
+ * INDEPENDENCE (cvgs_execute_many): such a chain states read.table_src_lo / table_src_hi = the byte range of the WHOLE frame, which is
+ * cvgs_plane_table_hull of the one whole-frame view (chroma rows included).  Every box is clamped into the frame, whatever the device
+ * writes, so that range holds every byte the table's planes can read: exact enough, and always safe.
+ * Validation happens completely on the host before the first HIP call (a machine without a GPU can test it): null pointers, struct_size,
+ * flags, n outside 1..CVGS_MAX_CHAINS, max_boxes outside 1..65535, misaligned pointers (table_out: 8 bytes; boxes / count / rects_out: 4),
+ * the frame checks of the host lowering -> CVGS_ERR_INVALID; per-pixel (CVGS_READ_PIXEL / CVGS_READ_NV12) and warp read kinds, YUV
+ * layouts other than NV12 / NV21 (device tables carry no layout tag), frames or targets beyond CVGS_MAX_DIM, targets for which
+ * dst_height * frame.width or dst_width * frame.height exceeds 2^30 -> CVGS_ERR_UNSUPPORTED.  The tables and rectangle buffers of one call
+ * must not overlap.  No reference counterpart.                                                                                      */
+typedef enum cvgs_box_format { CVGS_BOX_XYXY_F32 = 0, CVGS_BOX_XYWH_I32 = 1 } cvgs_box_format;
+typedef struct cvgs_box_table_desc {
+    uint32_t struct_size, flags;      /* sizeof(cvgs_box_table_desc); flags: must be 0 */
+    cvgs_image2d frame;               /* the WHOLE frame / surface (device pointer) */
+    int32_t read_kind;                /* CVGS_READ_RESIZE_LINEAR or CVGS_READ_NV12_RESIZE_LINEAR */
+    int32_t src_type, yuv_layout;     /* NV12 kind: CVGS_YUV_NV12 / NV21 only (what device tables serve today) */
+    int32_t dst_width, dst_height, aspect_ratio;
+    int32_t box_format, max_boxes;    /* cvgs_box_format; 1..65535 */
+    const void* boxes;                /* device: max_boxes x 4 floats / int32 */
+    const int32_t* count;             /* device, or NULL */
+    void* table_out;                  /* device, cvgs_plane_table_bytes(max_boxes) */
+    int32_t* rects_out;               /* device, or NULL */
+} cvgs_box_table_desc;
+int cvgs_plane_tables_from_boxes(const cvgs_box_table_desc* descs, int32_t n, cvgs_stream_t stream);
 
 #ifdef __cplusplus
 }

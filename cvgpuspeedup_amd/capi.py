@@ -114,6 +114,18 @@ class BoxTableDesc(C.Structure):
                 ("count", C.c_void_p), ("table_out", C.c_void_p), ("rects_out", C.c_void_p)]
 
 
+# device-built warp tables (include/cvgs_hip_ext.h: cvgs_warp_tables_from_points)
+WARP_FIT_SIMILARITY, WARP_FIT_AFFINE3 = 0, 1
+WARP_MAX_POINTS, WARP_MAX_FRAMES = 16, 16
+
+
+class WarpTableDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("frame", Image2D), ("src_type", C.c_int32), ("read_kind", C.c_int32),
+                ("dst_width", C.c_int32), ("dst_height", C.c_int32), ("fit", C.c_int32), ("n_points", C.c_int32),
+                ("tmpl", (C.c_float * 2) * WARP_MAX_POINTS), ("max_items", C.c_int32), ("reserved", C.c_int32), ("points", C.c_void_p),
+                ("count", C.c_void_p), ("table_out", C.c_void_p), ("valid_out", C.c_void_p)]
+
+
 # every symbol include/cvgs_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("cvgs_abi_version", C.c_int, []),
@@ -152,6 +164,9 @@ SYMBOLS = [
     ("cvgs_queue_profile", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("cvgs_queue_destroy", C.c_int, [C.c_void_p]),
     ("cvgs_plane_tables_from_boxes", C.c_int, [C.POINTER(BoxTableDesc), C.c_int32, C.c_void_p]),
+    ("cvgs_warp_table_bytes", C.c_size_t, [C.c_int32]),
+    ("cvgs_warp_tables_from_points", C.c_int, [C.POINTER(WarpTableDesc), C.c_int32, C.c_void_p]),
+    ("cvgs_warp_table_build_host", C.c_int, [C.POINTER(WarpTableDesc), C.c_void_p]),
     ("cvgs_range_push", None, [C.c_char_p]),
     ("cvgs_range_pop", None, []),
 ]

@@ -203,8 +203,12 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
     }
     if (is_warp(rd.kind)) {
         if (!rd.warp_dst_sizes && (rd.dst_width < 1 || rd.dst_height < 1)) return fail(CVGS_ERR_INVALID, "warp target must be positive");
-        if (!rd.warp_matrices) return fail(CVGS_ERR_INVALID, "read.warp_matrices is null");
-        if (rd.flags & CVGS_READ_FLAG_TABLE_ON_DEVICE) return fail(CVGS_ERR_UNSUPPORTED, "warp reads take host descriptors");
+        if (rd.flags & CVGS_READ_FLAG_TABLE_ON_DEVICE) {
+            // a caller-owned device warp table (cvgs_warp_tables_from_points): matrices and per-plane sizes live in the table
+            if (rd.warp_matrices || rd.warp_dst_sizes)
+                return fail(CVGS_ERR_INVALID, "device warp tables hold their own matrices and sizes: warp_matrices / warp_dst_sizes must be null");
+            if (sdepth == CVGS_DEPTH_64F) return fail(CVGS_ERR_UNSUPPORTED, "device warp tables: CV_64F sources take host descriptors");
+        } else if (!rd.warp_matrices) return fail(CVGS_ERR_INVALID, "read.warp_matrices is null");
     }
     if (is_resize(rd.kind)) {
         if (rd.dst_width < 1 || rd.dst_height < 1) return fail(CVGS_ERR_INVALID, "resize target must be positive");
@@ -902,7 +906,7 @@ int dispatch(const cvgs_chain_desc* ch, Lowered& L, hipStream_t stream, bool dry
     }
     if (warp) {
         if (has_mirrors) return fail(CVGS_ERR_UNSUPPORTED, "mirrors on warp chains");
-        const WarpPlane* dev = nullptr;
+        const WarpPlane* dev = (const WarpPlane*)L.args.read.table; // a caller-owned device warp table (nothing is staged), or null
         const int n = (int)L.warp_planes.size();
         if (up_src) dev = dry_run ? (const WarpPlane*)(uintptr_t)16 : (const WarpPlane*)up.put(L.warp_planes.data(), L.warp_planes.size() * sizeof(WarpPlane));
         if (up.slot >= 0) {
@@ -1484,6 +1488,110 @@ int cvgs_plane_tables_from_boxes(const cvgs_box_table_desc* descs, int32_t n, cv
     return CVGS_OK;
 }
 
+// Device warp tables from device-side landmarks (include/cvgs_hip_ext.h).  Everything is validated here, on the host, before the first HIP
+// call; the fit itself (cvgs_geometry.h: warp_fit) is one text for the kernel (k_points.hip) and for cvgs_warp_table_build_host.
+size_t cvgs_warp_table_bytes(int32_t planes) { return planes > 0 ? (size_t)planes * sizeof(WarpPlane) : 0; }
+
+namespace {
+// `host`: cvgs_warp_table_build_host -- desc.table_out is not used
+int check_warp_table_desc(const cvgs_warp_table_desc& d, bool host, PointFrame& f) {
+    if (d.struct_size != sizeof(cvgs_warp_table_desc)) return fail(CVGS_ERR_INVALID, "cvgs_warp_table_desc size mismatch (ABI)");
+    if (d.flags) return fail(CVGS_ERR_INVALID, "warp_tables_from_points: flags must be 0");
+    if (d.read_kind < CVGS_READ_PIXEL || d.read_kind > CVGS_READ_WARP_PERSPECTIVE) return fail(CVGS_ERR_INVALID, "bad read kind");
+    if (!is_warp(d.read_kind)) return fail(CVGS_ERR_UNSUPPORTED, "warp_tables_from_points: warp tables serve the warp reads (WARP_AFFINE / WARP_PERSPECTIVE) only");
+    if (d.max_items < 1 || d.max_items > 65535) return fail(CVGS_ERR_INVALID, "max_items must be in [1, 65535]");
+    if (d.fit != CVGS_WARP_FIT_SIMILARITY && d.fit != CVGS_WARP_FIT_AFFINE3) return fail(CVGS_ERR_INVALID, "bad warp fit");
+    if (d.fit == CVGS_WARP_FIT_SIMILARITY && (d.n_points < 2 || d.n_points > CVGS_WARP_MAX_POINTS))
+        return fail(CVGS_ERR_INVALID, "warp_tables_from_points: the similarity fit takes 2..16 points");
+    if (d.fit == CVGS_WARP_FIT_AFFINE3 && d.n_points != 3) return fail(CVGS_ERR_INVALID, "warp_tables_from_points: the AFFINE3 fit takes exactly 3 points");
+    if (!d.points) return fail(CVGS_ERR_INVALID, "warp_tables_from_points: points is null");
+    if (!host && !d.table_out) return fail(CVGS_ERR_INVALID, "warp_tables_from_points: table_out is null");
+    if ((!host && ((uintptr_t)d.table_out & 7)) || (((uintptr_t)d.points | (uintptr_t)d.count | (uintptr_t)d.valid_out) & 3))
+        return fail(CVGS_ERR_INVALID, "warp_tables_from_points: table_out needs 8-byte, points / count / valid_out 4-byte alignment");
+    if (d.dst_width < 1 || d.dst_height < 1) return fail(CVGS_ERR_INVALID, "warp target must be positive");
+    if (d.dst_width > kMaxDim || d.dst_height > kMaxDim) return fail(CVGS_ERR_UNSUPPORTED, "warp target wider or taller than 2^24 pixels");
+    // the template
+    bool coincide = true;
+    for (int i = 0; i < d.n_points; ++i) {
+        if (!fit_finite((double)d.tmpl[i][0]) || !fit_finite((double)d.tmpl[i][1])) return fail(CVGS_ERR_INVALID, "warp_tables_from_points: template entry is not finite");
+        coincide = coincide && d.tmpl[i][0] == d.tmpl[0][0] && d.tmpl[i][1] == d.tmpl[0][1];
+    }
+    if (d.fit == CVGS_WARP_FIT_SIMILARITY && coincide) return fail(CVGS_ERR_INVALID, "warp_tables_from_points: the template's points all coincide");
+    if (d.fit == CVGS_WARP_FIT_AFFINE3) {
+        const double q0x = (double)d.tmpl[0][0], q0y = (double)d.tmpl[0][1];
+        const double e1x = (double)d.tmpl[1][0] - q0x, e1y = (double)d.tmpl[1][1] - q0y, e2x = (double)d.tmpl[2][0] - q0x, e2y = (double)d.tmpl[2][1] - q0y;
+        const double det = e1x * e2y - e1y * e2x; // as warp_fit forms it
+        if (det == 0.0 || !fit_finite(det)) return fail(CVGS_ERR_INVALID, "warp_tables_from_points: the AFFINE3 template has zero area");
+    }
+    // the frame, as lower() checks a host-described warp source
+    const cvgs_image2d& im = d.frame;
+    const int sdepth = type_depth(d.src_type);
+    const int esz = depth_bytes(sdepth) * CVGS_TYPE_CN(d.src_type);
+    if (CVGS_TYPE_CN(d.src_type) > 4 || esz < 1) return fail(CVGS_ERR_INVALID, "bad source type");
+    if (sdepth == CVGS_DEPTH_64F) return fail(CVGS_ERR_UNSUPPORTED, "device warp tables: CV_64F sources take host descriptors");
+    if (!im.data || im.width < 1 || im.height < 1) return fail(CVGS_ERR_INVALID, "empty source plane");
+    if (im.width > kMaxDim || im.height > kMaxDim) return fail(CVGS_ERR_UNSUPPORTED, "source plane wider or taller than 2^24 pixels");
+    if ((int64_t)im.step < (int64_t)im.width * esz) return fail(CVGS_ERR_INVALID, "source step smaller than a row");
+    if (im.uv_offset) return fail(CVGS_ERR_INVALID, "warp_tables_from_points: uv_offset belongs to the NV12 kinds");
+    f = PointFrame{};
+    f.data = (const uint8_t*)im.data;
+    f.points = d.points;
+    f.count = d.count;
+    f.table = (WarpPlane*)d.table_out;
+    f.valid = d.valid_out;
+    f.w = im.width; f.h = im.height; f.step = im.step;
+    f.dst_w = d.dst_width; f.dst_h = d.dst_height;
+    f.fit = d.fit; f.n_points = d.n_points;
+    f.max_items = d.max_items;
+    for (int i = 0; i < d.n_points; ++i) { f.tmpl[2 * i] = d.tmpl[i][0]; f.tmpl[2 * i + 1] = d.tmpl[i][1]; }
+    return CVGS_OK;
+}
+} // namespace
+
+int cvgs_warp_tables_from_points(const cvgs_warp_table_desc* descs, int32_t n, cvgs_stream_t stream) {
+    if (!descs) return fail(CVGS_ERR_INVALID, "warp_tables_from_points: null descriptors");
+    if (n < 1 || n > CVGS_WARP_MAX_FRAMES) return fail(CVGS_ERR_INVALID, "warp_tables_from_points: n must be in [1, 16]");
+    PointFrame frames[CVGS_WARP_MAX_FRAMES];
+    ByteRange outs[2 * CVGS_WARP_MAX_FRAMES];
+    int n_outs = 0;
+    for (int i = 0; i < n; ++i) {
+        const int rc = check_warp_table_desc(descs[i], false, frames[i]);
+        if (rc) return rc;
+        const PointFrame& f = frames[i];
+        outs[n_outs++] = ByteRange{(const uint8_t*)f.table, (const uint8_t*)f.table + (size_t)f.max_items * sizeof(WarpPlane)};
+        if (f.valid) outs[n_outs++] = ByteRange{(const uint8_t*)f.valid, (const uint8_t*)f.valid + (size_t)f.max_items * sizeof(int32_t)};
+    }
+    for (int i = 0; i < n_outs; ++i)
+        for (int j = 0; j < i; ++j)
+            if (outs[i].lo < outs[j].hi && outs[j].lo < outs[i].hi) return fail(CVGS_ERR_INVALID, "warp_tables_from_points: the output buffers of one call overlap");
+    const int e = launch_points(frames, n, stream);
+    if (e) return hip_fail((hipError_t)e, "warp_tables_from_points: kernel launch");
+    return CVGS_OK;
+}
+
+int cvgs_warp_table_build_host(const cvgs_warp_table_desc* desc, void* table_out_host) {
+    if (!desc || !table_out_host) return fail(CVGS_ERR_INVALID, "warp_table_build_host: null argument");
+    PointFrame f;
+    const int rc = check_warp_table_desc(*desc, true, f);
+    if (rc) return rc;
+    int live = f.count ? *f.count : f.max_items;
+    live = live < 0 ? 0 : (live > f.max_items ? f.max_items : live);
+    for (int i = 0; i < f.max_items; ++i) { // k_points' body
+        WarpPlane P;
+        std::memset(&P, 0, sizeof(P));
+        P.data = f.data;
+        P.w = f.w;
+        P.h = f.h;
+        P.step = f.step;
+        P.dw = f.dst_w;
+        P.dh = f.dst_h;
+        const bool ok = warp_fit(f.fit, f.n_points, f.points + (size_t)i * (size_t)f.n_points * 2, f.tmpl, i < live, P.m);
+        std::memcpy((uint8_t*)table_out_host + (size_t)i * sizeof(WarpPlane), &P, sizeof(P));
+        if (f.valid) f.valid[i] = ok ? 1 : 0;
+    }
+    return CVGS_OK;
+}
+
 // ---- CircularTensor ------------------------------------------------------------------------------
 struct cvgs_circular_s {
     int32_t width, height, elem_type, color_planes, batch, order, cp_mode, device;
@@ -1567,6 +1675,8 @@ int cvgs_circular_update(cvgs_circular_t ct, const cvgs_chain_desc* chain, cvgs_
             return fail(CVGS_ERR_UNSUPPORTED, "CircularTensor::update cannot be captured into a graph (host-side ring index): create the "
                                               "handle with CVGS_CIRCULAR_CAPTURABLE");
     }
+    if (is_warp(chain->read.kind) && (chain->read.flags & CVGS_READ_FLAG_TABLE_ON_DEVICE))
+        return fail(CVGS_ERR_UNSUPPORTED, "CircularTensor::update: warp reads over a device table are not served (host descriptors)");
     cvgs_chain_desc one = *chain;
     if (one.read.batch != 1) return fail(CVGS_ERR_INVALID, "CircularTensor::update pushes one frame: batch must be 1");
     const int wk = one.write.kind;

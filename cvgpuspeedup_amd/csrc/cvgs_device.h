@@ -303,6 +303,24 @@ static constexpr int kBoxFramesSmall = 16; // a tick of 16 cameras: a 1.5 KB arg
 // validated by the caller; frames[0..n), n <= CVGS_MAX_CHAINS.  0 or a HIP error code
 int launch_boxes(const BoxFrame* frames, int n, void* stream);
 
+// ---- device-built warp tables (k_points.hip): one frame's part of a cvgs_warp_tables_from_points launch, 200 bytes ---------------
+struct PointFrame {
+    const uint8_t* data;     // the whole frame
+    const float* points;     // [max_items][n_points][2]
+    const int32_t* count;    // live items, or nullptr = max_items
+    WarpPlane* table;        // out: WarpPlane[max_items]
+    int32_t* valid;          // out: int32[max_items], or nullptr
+    int32_t w, h, step;
+    int32_t dst_w, dst_h;
+    int32_t fit, n_points;   // cvgs_warp_fit
+    int32_t max_items;
+    float tmpl[2 * CVGS_WARP_MAX_POINTS];
+};
+static_assert(sizeof(PointFrame) == 200, "PointFrame layout");
+static_assert(sizeof(PointFrame) * CVGS_WARP_MAX_FRAMES <= 4096, "the descriptors and templates of one launch fit a 4 KB argument block");
+// validated by the caller; frames[0..n), n <= CVGS_WARP_MAX_FRAMES.  0 or a HIP error code
+int launch_points(const PointFrame* frames, int n, void* stream);
+
 // ---- device-side arrival flags of the P2P fused-write exchange (k_exchange.hip) ----------------------------------------------
 #define CVGS_MAX_EXCHANGE_PEERS 16
 int launch_exchange_signal(void* const* peer_flags, int n, uint64_t value, uint64_t* counter, void* stream);

@@ -1,5 +1,5 @@
-// cvgs_geometry.h -- the per-plane resize geometry and the box -> rectangle rule, ONE spelling for the host-side lowering (cvgs_api.cpp)
-// and the device-side table builder (k_boxes.hip).  Bit-exactness of fx / fy is part of the parity contract: both sides compile this text
+// cvgs_geometry.h -- the per-plane resize geometry, the box -> rectangle rule and the landmark -> warp fit, ONE spelling for the host side
+// (cvgs_api.cpp) and the device-side table builders (k_boxes.hip, k_points.hip).  Bit-exactness of fx / fy is part of the parity contract: both sides compile this text
 // with -ffp-contract=off, gfx950 divides fp32 and fp64 correctly rounded (HIP's default), and roundf is exact on both -- so a table
 // written on the device equals the host-built one byte for byte (tests/test_gpu_boxes.py compares them).
 #pragma once
@@ -65,6 +65,85 @@ CVGS_HD inline void box_axis_snap_even(int extent, int* lo, int* hi) {
     *lo &= ~1;
     *hi = (*hi + 1) & ~1;
     if (*hi > extent) *hi = extent;
+}
+
+// ---- landmarks -> inverse warp (cvgs_hip_ext.h: cvgs_warp_fit) -------------------------------------------------------------------------
+// The K points of ONE item (`pts`: x0 y0 x1 y1 ..., frame pixels) and the template (`tmpl`: the same layout, destination pixels) become the
+// nine floats of a WarpPlane::m, DESTINATION -> SOURCE.  Returns false, with the invalid entry in m, when the item is invalid.  Everything is
+// computed in double in the order written here -- sums over the points in index order, no sqrt / sin / cos -- and narrowed to float at the
+// end: host and device compile this text with -ffp-contract=off and divide correctly rounded, so they agree bit for bit
+// (tests/test_gpu_warp_points.py).  `pts` is read in place (twice for the similarity fit), never copied into an array: on the device it
+// points into global memory and the function needs no scratch.  Whatever `pts` holds, m only decides WHERE inside the host-validated frame
+// a plane reads: the warp kernels test 0 <= sx < w && 0 <= sy < h before any tap, which NaN, +-inf and huge values all fail.
+CVGS_HD inline bool fit_finite(double v) { return v - v == 0.0; } // false for NaN and +-inf
+CVGS_HD inline void warp_fit_invalid(float* m) { // every destination pixel -> (-1, -1): outside any source
+    m[0] = 0.f; m[1] = 0.f; m[2] = -1.f;
+    m[3] = 0.f; m[4] = 0.f; m[5] = -1.f;
+    m[6] = 0.f; m[7] = 0.f; m[8] = 1.f;
+}
+// `live`: the item's index lies below the (clamped) count.  The caller has validated fit, k and the template on the host.
+CVGS_HD inline bool warp_fit(int fit, int k, const float* pts, const float* tmpl, bool live, float* m) {
+    warp_fit_invalid(m);
+    if (!live) return false;
+    double m0, m1, m2, m3, m4, m5;
+    if (fit == CVGS_WARP_FIT_AFFINE3) {
+        // M (q_j, 1) = p_j: the linear part maps the template's edge vectors onto the points' (Cramer's rule), the translation fixes point 0
+        const double p0x = (double)pts[0], p0y = (double)pts[1], p1x = (double)pts[2], p1y = (double)pts[3], p2x = (double)pts[4], p2y = (double)pts[5];
+        if (!(fit_finite(p0x) && fit_finite(p0y) && fit_finite(p1x) && fit_finite(p1y) && fit_finite(p2x) && fit_finite(p2y))) return false;
+        const double q0x = (double)tmpl[0], q0y = (double)tmpl[1];
+        const double e1x = (double)tmpl[2] - q0x, e1y = (double)tmpl[3] - q0y, e2x = (double)tmpl[4] - q0x, e2y = (double)tmpl[5] - q0y;
+        const double det = e1x * e2y - e1y * e2x; // != 0: checked on the host
+        const double d1x = p1x - p0x, d1y = p1y - p0y, d2x = p2x - p0x, d2y = p2y - p0y;
+        m0 = (d1x * e2y - d2x * e1y) / det;
+        m1 = (d2x * e1x - d1x * e2x) / det;
+        m3 = (d1y * e2y - d2y * e1y) / det;
+        m4 = (d2y * e1x - d1y * e2x) / det;
+        m2 = p0x - (m0 * q0x + m1 * q0y);
+        m5 = p0y - (m3 * q0x + m4 * q0y);
+    } else {
+        // forward fit p -> q: q ~ [a -b; b a] p + t, least squares in closed form
+        double px = 0.0, py = 0.0, qx = 0.0, qy = 0.0;
+        bool finite = true;
+        for (int i = 0; i < k; ++i) {
+            const double x = (double)pts[2 * i], y = (double)pts[2 * i + 1];
+            finite = finite && fit_finite(x) && fit_finite(y);
+            px = px + x;
+            py = py + y;
+            qx = qx + (double)tmpl[2 * i];
+            qy = qy + (double)tmpl[2 * i + 1];
+        }
+        if (!finite) return false;
+        const double kd = (double)k;
+        px = px / kd; py = py / kd; qx = qx / kd; qy = qy / kd;
+        double den = 0.0, sa = 0.0, sb = 0.0;
+        for (int i = 0; i < k; ++i) {
+            const double pcx = (double)pts[2 * i] - px, pcy = (double)pts[2 * i + 1] - py;
+            const double qcx = (double)tmpl[2 * i] - qx, qcy = (double)tmpl[2 * i + 1] - qy;
+            den = den + (pcx * pcx + pcy * pcy);
+            sa = sa + (pcx * qcx + pcy * qcy);
+            sb = sb + (pcx * qcy - pcy * qcx);
+        }
+        if (den == 0.0 || !fit_finite(den)) return false;
+        const double a = sa / den, b = sb / den;
+        const double tx = qx - (a * px - b * py), ty = qy - (b * px + a * py);
+        const double n = a * a + b * b;
+        if (n == 0.0 || !fit_finite(n)) return false;
+        // the inverse: p = (1/n) [a b; -b a] (q - t)
+        const double ia = a / n, ib = b / n;
+        m0 = ia;
+        m1 = ib;
+        m2 = -(ia * tx + ib * ty);
+        m3 = -ib;
+        m4 = ia;
+        m5 = ib * tx - ia * ty;
+    }
+    const float f0 = (float)m0, f1 = (float)m1, f2 = (float)m2, f3 = (float)m3, f4 = (float)m4, f5 = (float)m5;
+    if (!(fit_finite((double)f0) && fit_finite((double)f1) && fit_finite((double)f2) && fit_finite((double)f3) && fit_finite((double)f4) &&
+          fit_finite((double)f5)))
+        return false;
+    m[0] = f0; m[1] = f1; m[2] = f2;
+    m[3] = f3; m[4] = f4; m[5] = f5;
+    return true;
 }
 
 } // namespace cvgs

@@ -744,6 +744,71 @@ def resize_boxes(frame, table, max_boxes, dsize, background=None, ar=IGNORE_AR, 
     return rd
 
 
+# ---- device-built warp tables: aligned crops from a detector's device-side landmarks (include/cvgs_hip_ext.h) ----------------
+WARP_FIT_SIMILARITY, WARP_FIT_AFFINE3 = capi.WARP_FIT_SIMILARITY, capi.WARP_FIT_AFFINE3
+
+
+def warp_table_desc(frame, points, table, max_items, dsize, tmpl, fit=WARP_FIT_SIMILARITY, warp_type=WARP_AFFINE, count=None, valid=None):
+    """One cvgs_warp_table_desc: `frame` is the GpuMat of the WHOLE frame, `tmpl` the template points [(x, y), ...] in destination pixels
+    (their number is n_points); points / count / table / valid are device buffers (torch tensors or raw pointers): float32
+    [max_items][n_points][2], one int32 or None, 64 * max_items bytes, max_items int32 or None."""
+    d = capi.WarpTableDesc()
+    d.struct_size = C.sizeof(capi.WarpTableDesc)
+    d.frame = frame.image2d()
+    d.src_type = frame.cv_type
+    d.read_kind = capi.READ_WARP_AFFINE if warp_type == WARP_AFFINE else capi.READ_WARP_PERSPECTIVE
+    d.dst_width, d.dst_height = int(dsize[0]), int(dsize[1])
+    tmpl = [(float(x), float(y)) for x, y in tmpl]
+    if len(tmpl) > capi.WARP_MAX_POINTS:
+        raise ValueError("a template holds at most %d points" % capi.WARP_MAX_POINTS)
+    d.fit, d.n_points = fit, len(tmpl)
+    for i, (x, y) in enumerate(tmpl):
+        d.tmpl[i][0], d.tmpl[i][1] = x, y
+    d.max_items = int(max_items)
+    d.points, d.count, d.table_out, d.valid_out = _dev_ptr(points) or None, _dev_ptr(count) or None, _dev_ptr(table) or None, _dev_ptr(valid) or None
+    return d
+
+
+def warp_tables_from_points(stream, descs):
+    """cvgs_warp_tables_from_points: ONE small kernel on `stream` fits the transforms of every desc (warp_table_desc) to the landmarks in
+    device memory and writes the device warp tables; nothing is copied to the host, nothing synchronises, and the launch can be captured."""
+    lib = capi.load_library()
+    descs = list(descs)
+    arr = (capi.WarpTableDesc * len(descs))(*descs)
+    capi.check(lib.cvgs_warp_tables_from_points(arr, len(descs), stream_handle(stream)))
+
+
+def build_warp_table_host(desc, points, count=None):
+    """cvgs_warp_table_build_host: the table (bytes, 64 per item) and the validity flags (list of 0 / 1) the kernel must write for `desc`,
+    computed on the CPU from HOST `points` (anything numpy turns into float32 [max_items][n_points][2]) and `count` (int or None)."""
+    import numpy as np
+    lib = capi.load_library()
+    d = capi.WarpTableDesc.from_buffer_copy(desc)
+    pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1)
+    if pts.size != d.max_items * d.n_points * 2:
+        raise ValueError("points must hold max_items x n_points x 2 floats")
+    cnt = None if count is None else C.c_int32(int(count))
+    valid = (C.c_int32 * max(d.max_items, 1))()
+    out = (C.c_uint8 * (64 * max(d.max_items, 1)))()
+    d.points = pts.ctypes.data
+    d.count = None if cnt is None else C.addressof(cnt)
+    d.valid_out = C.addressof(valid)
+    capi.check(lib.cvgs_warp_table_build_host(C.byref(d), out))
+    return bytes(out), list(valid)
+
+
+def warp_table(warp_type, frame, table, max_items, dsize, used_planes=None, default_value=None):
+    """The batched read "warp over a device-built table of `frame`" (warp_tables_from_points): batch = max_items, planes at or beyond
+    used_planes take default_value, validity is per plane inside the table.  The chain states the whole frame's byte range."""
+    kind = capi.READ_WARP_AFFINE if warp_type == WARP_AFFINE else capi.READ_WARP_PERSPECTIVE
+    rd = ReadIOp(kind, frame.cv_type, None, used_planes, (int(dsize[0]), int(dsize[1])), IGNORE_AR, default_value, table=_dev_ptr(table),
+                 batch=int(max_items))
+    lo = int(frame.data)
+    rd.table_hull = (lo, lo + int(frame.step) * (int(frame.rows) - 1) + int(frame.cols) * elem_size(frame.cv_type))
+    rd.frame = frame  # (keeps the frame's storage alive with the IOp)
+    return rd
+
+
 class CircularTensor:
     """cvGS::CircularTensor<I, O, COLOR_PLANES, BATCH, ORDER, CP_MODE> (reference include/cvGPUSpeedup.cuh:600-627)."""
 

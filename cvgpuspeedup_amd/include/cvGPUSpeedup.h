@@ -658,6 +658,78 @@ inline auto resize(const DeviceCrops& crops, const cv::Scalar& backgroundValue_ 
     return rd;
 }
 
+// ---- aligned crops from a detector's device-side landmarks (engine extension: cvgs_warp_tables_from_points, include/cvgs_hip_ext.h) ----
+// Face alignment / oriented-box rectification without the host in the loop: the landmarks a network has just written on this GPU are
+// fitted to a template in ONE small kernel on the stream, and warp<WT, T>(deviceWarps) reads the resulting device warp table like any
+// other batched warp.  update() copies nothing to the host and never synchronises.
+//   cvGS::DeviceWarps faces(64);                                         // owns the table (and the validity buffer) of up to 64 items
+//   faces.update(stream, frame, d_landmarks, d_count, CVGS_WARP_FIT_SIMILARITY, arcface5, cv::Size(112, 112));
+//   cvGS::executeOperations(stream, cvGS::warp<fk::WarpType::Affine, CV_8UC3>(faces), ..., cvGS::split<CV_32FC3>(tensor, cv::Size(112, 112)));
+// Invalid items (a non-finite coordinate, coincident landmarks, at or beyond *d_count) give planes of 0 followed by the chain's program;
+// valid() (device int32[maxItems], 1 / 0) says which.
+class DeviceWarps {
+public:
+    explicit DeviceWarps(int maxItems, bool withValid = true) : max_(maxItems) {
+        if (maxItems < 1 || maxItems > 65535) throw std::runtime_error("cvGS::DeviceWarps: maxItems must be in [1, 65535]");
+        void* p = nullptr;
+        fk::hip_check(hipMalloc(&p, cvgs_warp_table_bytes(maxItems)), "hipMalloc(warp table)");
+        table_ = std::shared_ptr<void>(p, [](void* q) { (void)hipFree(q); });
+        if (withValid) {
+            fk::hip_check(hipMalloc(&p, (size_t)maxItems * sizeof(int32_t)), "hipMalloc(valid)");
+            valid_ = std::shared_ptr<void>(p, [](void* q) { (void)hipFree(q); });
+        }
+    }
+    // enqueue the builder for ONE frame: `points` = device float32 [maxItems][tmpl.size()][2] (x, y) in frame pixels; `count` = device int32
+    // or nullptr (= maxItems); `tmpl` = the template in destination pixels (SIMILARITY: 2..16 points, AFFINE3: 3).  The frame's type is taken
+    // from the GpuMat; the warp that reads the table may be affine or perspective.
+    void update(const cv::cuda::Stream& stream, const cv::cuda::GpuMat& frame, const float* points, const int32_t* count, cvgs_warp_fit fit,
+                const std::vector<cv::Point2f>& tmpl, const cv::Size& dsize) {
+        if (tmpl.size() > (size_t)CVGS_WARP_MAX_POINTS) throw std::runtime_error("cvGS::DeviceWarps::update: a template holds at most 16 points");
+        cvgs_warp_table_desc d;
+        std::memset(&d, 0, sizeof(d));
+        d.struct_size = sizeof(d);
+        d.frame = cvgs_image2d{frame.data, frame.cols, frame.rows, (int32_t)frame.step, 0};
+        d.src_type = frame.type();
+        d.read_kind = CVGS_READ_WARP_AFFINE;
+        d.dst_width = dsize.width; d.dst_height = dsize.height;
+        d.fit = (int32_t)fit; d.n_points = (int32_t)tmpl.size();
+        for (size_t i = 0; i < tmpl.size(); ++i) { d.tmpl[i][0] = tmpl[i].x; d.tmpl[i][1] = tmpl[i].y; }
+        d.max_items = max_;
+        d.points = points; d.count = count;
+        d.table_out = table_.get(); d.valid_out = static_cast<int32_t*>(valid_.get());
+        fk::detail::check_status(cvgs_warp_tables_from_points(&d, 1, cv::cuda::StreamAccessor::getStream(stream)));
+        frame_ = frame; dsize_ = dsize;
+    }
+    int maxItems() const { return max_; }
+    const void* table() const { return table_.get(); }
+    const int32_t* valid() const { return static_cast<const int32_t*>(valid_.get()); } // nullptr when built without
+    // what the last update() described
+    const cv::cuda::GpuMat& frame() const { return frame_; }
+    cv::Size dsize() const { return dsize_; }
+private:
+    int max_;
+    std::shared_ptr<void> table_, valid_;
+    cv::cuda::GpuMat frame_;
+    cv::Size dsize_;
+};
+
+// warp<WT, T>(deviceWarps[, defaultValue]): the batched warp over the device-built table -- maxItems planes of the size of the last update().
+// fk::executeDivergentBatch keeps refusing warps and device tables.
+template <fk::WarpType WT, int InputType = CV_8UC3>
+inline auto warp(const DeviceWarps& warps, const cv::Scalar& defaultValue = cv::Scalar()) {
+    const cv::cuda::GpuMat& f = warps.frame();
+    if (!f.data) throw std::runtime_error("cvGS::warp(DeviceWarps): update() has not described a frame yet");
+    if (f.type() != InputType) throw std::runtime_error("Input type does not match the input type of the operation.");
+    fk::DeviceTableWarpRead<WT, CUDA_T(InputType)> rd;
+    rd.table = warps.table();
+    rd.batch = rd.used = warps.maxItems();
+    rd.dsize = fk::Size(warps.dsize().width, warps.dsize().height);
+    for (int c = 0; c < CV_MAT_CN(InputType); ++c) rd.background[c] = static_cast<float>(defaultValue[c]);
+    rd.src_lo = f.data;
+    rd.src_hi = (const unsigned char*)f.data + (size_t)f.step * (size_t)(f.rows - 1) + (size_t)f.cols * f.elemSize();
+    return rd;
+}
+
 // ---- launch batching (engine extension, see fk::ChainBatch): several independent chains, ONE kernel launch -------------
 class ChainBatch {
 public:

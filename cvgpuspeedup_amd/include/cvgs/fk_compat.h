@@ -756,6 +756,31 @@ template <WarpType WT, typename T> struct WarpRead {
     }
 };
 
+// The batched warp over a DEVICE warp table that cvgs_warp_tables_from_points fitted to a detector's device-side landmarks
+// (cvGS::DeviceWarps): batch = the table's entries, planes at or beyond `used` take the default value, validity is per plane inside the table.
+template <WarpType WT, typename T> struct DeviceTableWarpRead {
+    const void* table = nullptr;
+    int batch = 0, used = 0;
+    Size dsize;
+    float background[4] = {0, 0, 0, 0};
+    const void* src_lo = nullptr;
+    const void* src_hi = nullptr;
+    using OutputType = VectorType_t<float, cn<T>>;
+    static constexpr Stage stage = Stage::Read;
+    void lower(ChainBuilder& b) const {
+        cvgs_read_desc& r = b.d.read;
+        r.kind = WT == WarpType::Affine ? CVGS_READ_WARP_AFFINE : CVGS_READ_WARP_PERSPECTIVE;
+        r.src_type = cvGS::cv_type_of<T>;
+        r.batch = batch; r.used_planes = used;
+        r.src = table; r.flags = CVGS_READ_FLAG_TABLE_ON_DEVICE;
+        r.table_src_lo = src_lo; r.table_src_hi = src_hi;
+        r.dst_width = dsize.width; r.dst_height = dsize.height;
+        for (int i = 0; i < 4; ++i) r.background[i] = background[i];
+        b.warp.clear();
+        b.warp_sizes.clear();
+    }
+};
+
 template <typename Op> template <size_t N> inline auto Read<Op>::then(const BatchCropSpec<N>& c) const {
     using T = typename Op::OutputType;
     BatchPixelRead<T> rd;

@@ -2,7 +2,8 @@
  * cvgs_hip_ext.h -- ENGINE EXTENSIONS of libcvgs_hip.so that have no counterpart in the reference's interface: the device-side
  * descriptor queue (cvgs_queue_*: an opt-in submission path, frozen since round 5), the device-side arrival flags of the sharded
  * batched-crop path (cvgs_exchange_*: BASELINE cfg #5, SURVEY.md 8e option 2) and plane tables built on the device from a detector's
- * device-side boxes (cvgs_plane_tables_from_boxes).  The drop-in boundary -- what replaces
+ * device-side boxes (cvgs_plane_tables_from_boxes) and warp tables fitted on the device to its device-side landmarks
+ * (cvgs_warp_tables_from_points).  The drop-in boundary -- what replaces
  * fk::executeOperations and fk::CircularTensor (reference include/cvGPUSpeedup.cuh:464-627) -- is include/cvgs_hip.h alone; nothing
  * there depends on this file.  Same conventions: plain C, asynchronous on the given stream, 0 or a negative cvgs_status.
  */
@@ -198,6 +199,71 @@ typedef struct cvgs_box_table_desc {
     int32_t* rects_out;               /* device, or NULL */
 } cvgs_box_table_desc;
 int cvgs_plane_tables_from_boxes(const cvgs_box_table_desc* descs, int32_t n, cvgs_stream_t stream);
+
+/* ---- device-built warp tables: aligned crops from a detector's device-side landmarks ---------------------------------------------------
+ * cvGS::warp is the other second-stage read: align N faces to a 5-point template, rectify N oriented detections, hand them to the
+ * network.  cvgs_warp_tables_from_points enqueues ONE small kernel on `stream` (csrc/k_points.hip) that fits the transforms where the
+ * landmarks are and writes the device warp tables of up to 16 frames (grid y = frame, one work-item per item; descriptors and templates
+ * travel in the kernel arguments).  Nothing is allocated, staged or synchronised; the launch can be captured between the producer of the
+ * points and the chains that read the tables.  Its cost has not been timed.
+ *
+ * A table entry is 64 bytes: {data, width, height, step} of the frame, float m[9] (row-major 3x3, DESTINATION -> SOURCE: what the warp
+ * kernels consume), {dst_width, dst_height}.  Coordinates follow the warp kernels' convention, which is cv::warpAffine's: integer
+ * coordinates are pixel centres.  The fit is computed in double, in one written order shared by host and device (csrc/cvgs_geometry.h:
+ * warp_fit; sums over the points in index order, no sqrt / sin / cos, -ffp-contract=off, correctly rounded division) and narrowed to float
+ * at the end, so the device-built table equals cvgs_warp_table_build_host byte for byte.
+ *   CVGS_WARP_FIT_SIMILARITY  n_points = 2..16 landmarks p_i (frame pixels) and the template q_i (destination pixels): the least-squares
+ *                             NON-REFLECTIVE similarity taking p -> q (the forward fit of skimage's SimilarityTransform / insightface's
+ *                             estimate_norm), in closed form -- with centred pc, qc and den = sum |pc|^2: a = sum pc.qc / den,
+ *                             b = sum (pc.x qc.y - pc.y qc.x) / den, t = mean(q) - [a -b; b a] mean(p) -- then inverted in closed form
+ *                             (n = a^2 + b^2).  Row 2 is 0 0 1.
+ *   CVGS_WARP_FIT_AFFINE3     exactly three points and a three-point template (three corners of an oriented box): the exact affine with
+ *                             M (q_j, 1) = p_j, by Cramer's rule on the template's edge vectors.  Row 2 is 0 0 1.
+ * An item is INVALID when any of its 2 * n_points coordinates is not finite; (similarity) den == 0, n == 0 or either is not finite; any of
+ * the six narrowed floats is not finite; or its index is at or beyond `count` (device int32, or NULL = max_items; clamped to
+ * [0, max_items]).  An invalid item gets m = {0,0,-1, 0,0,-1, 0,0,1}: every destination pixel maps to (-1, -1), outside the source, which
+ * every warp kernel renders as 0 followed by the chain's program -- the plane reads nothing.  valid_out (optional, device
+ * int32[max_items]) receives 1 / 0.
+ * WHY THE TABLE IS SAFE WHATEVER THE DEVICE BUFFER HOLDS: the warp kernels test 0 <= sx < width && 0 <= sy < height before any tap, and
+ * width / height / step / data of every entry are the frame the HOST validated here; NaN, +-inf and huge matrices all fail that test and
+ * give 0.  The points only ever decide WHERE inside the frame a plane reads.
+ * USING THE TABLE: a warp chain (CVGS_READ_WARP_AFFINE / _PERSPECTIVE) passes table_out as read.src with CVGS_READ_FLAG_TABLE_ON_DEVICE,
+ * batch = max_items (<= 65535), used_planes <= batch (planes beyond it take the default value), dst_width / dst_height = the builder's,
+ * warp_matrices == NULL and warp_dst_sizes == NULL (either non-null: CVGS_ERR_INVALID).  The launch reads the caller's table where a
+ * host-described batch beyond the inline limit reads an uploaded copy: nothing is staged, and cvgs_kernel_name gives the names of
+ * host-described chains of the same shape (a CV_64F program: the table variant, which host-described batches of more than 8 planes get).
+ * CV_64F sources are served through host descriptors only.  cvgs_execute_many runs such chains one by one (as every warp); the descriptor
+ * queue and cvgs_circular_update refuse them (CVGS_ERR_UNSUPPORTED, before anything is enqueued).  The chain may state
+ * read.table_src_lo / _hi = the whole frame's byte range.
+ * Validation happens completely on the host before the first HIP call: null pointers, struct_size, flags, n outside 1..16, max_items
+ * outside 1..65535, misaligned pointers (table_out: 8 bytes; points / count / valid_out: 4), n_points outside the fit's range, non-finite
+ * template entries, a similarity template whose points all coincide, an AFFINE3 template of zero area, a non-positive target, a frame
+ * that the host lowering would refuse, output buffers of one call that overlap -> CVGS_ERR_INVALID; non-warp read kinds, frames or
+ * targets beyond CVGS_MAX_DIM, CV_64F sources -> CVGS_ERR_UNSUPPORTED.
+ *   cvgs_warp_table_build_host  the same descriptor with HOST `points`, `count` and (optional) `valid_out`; desc->table_out is ignored and
+ *                               the table goes to table_out_host.  Runs the shared fit on the CPU and writes the bytes the kernel must
+ *                               write; makes no HIP call.
+ * No reference counterpart.                                                                                                          */
+typedef enum cvgs_warp_fit { CVGS_WARP_FIT_SIMILARITY = 0, CVGS_WARP_FIT_AFFINE3 = 1 } cvgs_warp_fit;
+#define CVGS_WARP_MAX_POINTS 16
+#define CVGS_WARP_MAX_FRAMES 16
+typedef struct cvgs_warp_table_desc {
+    uint32_t struct_size, flags;      /* sizeof(cvgs_warp_table_desc); flags: must be 0 */
+    cvgs_image2d frame;               /* the WHOLE frame (device pointer) */
+    int32_t src_type;
+    int32_t read_kind;                /* CVGS_READ_WARP_AFFINE or CVGS_READ_WARP_PERSPECTIVE */
+    int32_t dst_width, dst_height;
+    int32_t fit, n_points;            /* cvgs_warp_fit; SIMILARITY: 2..16, AFFINE3: 3 */
+    float tmpl[CVGS_WARP_MAX_POINTS][2]; /* template points (x, y) in destination pixels; entries beyond n_points are ignored */
+    int32_t max_items, reserved;      /* 1..65535; 0 */
+    const float* points;              /* device: float32 [max_items][n_points][2] (x, y) in frame pixels */
+    const int32_t* count;             /* device, or NULL */
+    void* table_out;                  /* device, cvgs_warp_table_bytes(max_items) */
+    int32_t* valid_out;               /* device, or NULL */
+} cvgs_warp_table_desc;
+size_t cvgs_warp_table_bytes(int32_t planes);
+int cvgs_warp_tables_from_points(const cvgs_warp_table_desc* descs, int32_t n, cvgs_stream_t stream);
+int cvgs_warp_table_build_host(const cvgs_warp_table_desc* desc, void* table_out_host);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,7 @@
 
 Written from the published definitions -- OpenCV-CUDA's resize_linear (no half-pixel offset, floor, +1 tap clamped to the last
 column / row, weights from the unclamped neighbour), the BT.601 / BT.709 / BT.2020 luma weights (Kr, Kb), the FOURCC layouts (NV12,
-NV21, I420, YV12, P010, YUYV, UYVY), cv::saturate_cast (round to nearest even, clamp, NaN -> 0) and IEEE binary16 / bfloat16 rounding --
+NV21, I420, YV12, P010, YUYV, UYVY, I444), cv::saturate_cast (round to nearest even, clamp, NaN -> 0) and IEEE binary16 / bfloat16 rounding --
 and NOT from oracle/cvgs_oracle.c.  Nothing here imports oracle/ or the product package: the iop objects the tests build are read by
 attribute only, and the numeric codes below are those of the public C header (include/cvgs_hip.h).
 
@@ -46,7 +46,7 @@ DEPTH_16BF = DEPTH_16F | FLAG_BF16
 READ_PIXEL, READ_RESIZE, READ_YUV, READ_YUV_RESIZE, READ_WARP_AFFINE, READ_WARP_PERSPECTIVE = range(6)
 PRESERVE_AR, IGNORE_AR, PRESERVE_AR_RN_EVEN, PRESERVE_AR_LEFT = 0, 1, 2, 3
 FULL, LIMITED = 0, 1
-NV12, NV21, I420, YV12, P010, YUYV, UYVY = range(7)
+NV12, NV21, I420, YV12, P010, YUYV, UYVY, I444 = range(8)
 BT601, BT709, BT2020 = 0, 1, 2
 (OP_NOP, OP_CAST, OP_MUL, OP_ADD, OP_SUB, OP_DIV, OP_REORDER, OP_ADD_ALPHA, OP_DROP_ALPHA, OP_GRAY, OP_CAST_TRUNC) = range(11)
 WRITE_PIXEL_2D, WRITE_PIXEL_3D, WRITE_SPLIT, WRITE_T_SPLIT = 0, 1, 2, 3
@@ -71,6 +71,7 @@ SPEC = {
     "ar_extent_truncated": False,       # PRESERVE_AR: fitted extent truncated instead of rounded
     "warp_border_replicate": False,     # warp: outside pixels replicate the border instead of being zero
     "coefficient_digit_off": False,     # the sixth decimal of every chroma coefficient off by one
+    "i444_chroma_subsampled": False,    # I444 chroma taken at (x / 2, y / 2), the 4:2:0 index, instead of the luma's own (x, y)
 }
 
 
@@ -119,7 +120,8 @@ def widen(arr, depth):
 
 class View:
     """A crop (x, y, w, h) of a surface held in a numpy array.  Plain images: (H, W[, C]).  4:2:0 surfaces: the whole (luma_h * 3 / 2, W)
-    array with `luma_h` luma rows.  Packed 4:2:2: (H, W, 2).  A padded pitch is a crop of a wider array."""
+    array with `luma_h` luma rows.  Packed 4:2:2: (H, W, 2).  Planar 4:4:4: the three planes stacked, (3, H, W), with x, y, w, h given.
+    A padded pitch is a crop of a wider array."""
 
     def __init__(self, arr, x=0, y=0, w=None, h=None, luma_h=None):
         self.arr, self.x, self.y, self.luma_h = arr, int(x), int(y), luma_h
@@ -203,7 +205,7 @@ def convert_yuv(yuv, yuv_b, color_range, primaries, ten_bit, alpha, sw=SPEC):
 
 def yuv_taps(view, layout, ty, tx, sw=SPEC):
     """Y, U, V codes (float64, (..., 3)) of the crop's pixels (ty, tx).  Chroma of a pixel is the sample of its 2x2 block (4:2:0) or of
-    its horizontal pair (4:2:2) in SURFACE coordinates."""
+    its horizontal pair (4:2:2) in SURFACE coordinates; 4:4:4 has one chroma sample per pixel, at the luma's own coordinates."""
     a = view.arr
     if sw["yuyv_uyvy_swapped"] and layout in (YUYV, UYVY):
         layout = UYVY if layout == YUYV else YUYV
@@ -215,6 +217,9 @@ def yuv_taps(view, layout, ty, tx, sw=SPEC):
         px = np.minimum(px, a.shape[1] // 2 - 1)
         row = sy if not sw["chroma_from_crop_origin"] else cy
         y_, u_, v_ = a[sy, sx, yi], a[row, 2 * px, ci], a[row, 2 * px + 1, ci]
+    elif layout == I444:
+        px, py = (cx // 2, cy // 2) if sw["i444_chroma_subsampled"] else (cx, cy)
+        y_, u_, v_ = a[0, sy, sx], a[1, py, px], a[2, py, px]
     else:
         H, W = view.luma_h, a.shape[1]
         if sw["chroma_rounds_up"]:

@@ -227,6 +227,34 @@ def yuv_case(layout, rng, prim, alpha, dst, crop=None, kind="random", pitch=0, w
     return build
 
 
+def yuv444_case(rng, prim, alpha, dst, crop=None, kind="random", w=48, h=32, tail="none", seed=7):
+    """Planar 4:4:4 (I444): three w x h planes behind one another; a crop (any origin, odd ones included) is also what a padded pitch is.
+    The oracle's value is composed (tests/yuv444_cases.Expect) from B.surfs444."""
+    def build(B):
+        from tests import yuv444_cases as Y444
+        ck = "checker" if kind == "chroma_checker" else kind
+        y = np.full((h, w), 120, np.uint8) if kind == "chroma_checker" else pattern((h, w), kind, seed)
+        u, v = pattern((h, w), ck, seed + 1), pattern((h, w), ck, seed + 2)[:, ::-1].copy()
+        surf = Y444.Surf(w, h, seed, planes=(y, u, v))
+        cn = 4 if alpha else 3
+        f = cvgs.make_type(cvgs.CV_32F, cn)
+        x, y0, cw, chh = crop if crop is not None else (0, 0, w, h)
+        m = B.src(surf.buf.reshape(3 * h, w), cvgs.CV_8UC1)
+        luma = cvgs.GpuMat(h, w, cvgs.CV_8UC1, m.data, m.step, owner=m.owner)
+        luma.uv_offset = h * m.step
+        B.surfs444 = [surf]
+        rd = cvgs.read_yuv444(luma.yuv444_roi(x, y0, cw, chh), dst, rng, prim, alpha)
+        ops = normalise(cn) if tail == "normalise" else []
+        if dst is None:
+            wr = cvgs.write(f, B.out((chh, cw, cn), f))
+        else:
+            wr = cvgs.split(f, B.out((1, cn * dst[0] * dst[1]), cvgs.CV_32FC1), dst)
+        return [rd] + ops + [wr], [F.View(np.stack([y, u, v]), x, y0, cw, chh)]
+    build.layout422 = None
+    build.layout444 = True
+    return build
+
+
 def affine_matrix(angle_deg, scale, tx, ty, centre):
     a = np.deg2rad(angle_deg)
     c, s = np.cos(a) * scale, np.sin(a) * scale
@@ -335,6 +363,17 @@ for _l, _ln in LAYOUT_NAMES.items():
         add("yuv_rs_%s_crop" % _ln, "YUV " + _ln, yuv_case(_l, capi.YUV_LIMITED, capi.BT709, False, (21, 13), crop=(6, 12, 30, 18), kind="chroma_checker"), _fast)
         add("yuv_px_%s_crop" % _ln, "YUV " + _ln, yuv_case(_l, capi.YUV_FULL, capi.BT601, True, None, crop=(10, 4, 22, 10)))
         add("yuv_rs_%s_pitch" % _ln, "YUV " + _ln, yuv_case(_l, capi.YUV_FULL, capi.BT2020, False, (21, 13), pitch=16), _fast)
+
+# planar 4:4:4: a conversion of each range, the siting patterns (a chroma checkerboard shows an index taken from the 4:2:0 rule), crops at odd
+# origins (which is also what a padded pitch is), up-scaling into the headline chain
+add("yuv_px_i444_r0_p0_a0", "YUV i444", yuv444_case(capi.YUV_FULL, capi.BT601, False, None, seed=30))
+add("yuv_rs_i444_r1_p1_a0", "YUV i444", yuv444_case(capi.YUV_LIMITED, capi.BT709, False, (29, 19), seed=41), "k_yuv444_resize")
+add("yuv_rs_i444_r1_p2_a1", "YUV i444", yuv444_case(capi.YUV_LIMITED, capi.BT2020, True, (29, 19), seed=42))
+add("yuv_px_i444_chroma_checker", "YUV i444", yuv444_case(capi.YUV_FULL, capi.BT601, False, None, kind="chroma_checker"))
+add("yuv_rs_i444_ramp_h", "YUV i444", yuv444_case(capi.YUV_LIMITED, capi.BT709, False, (37, 23), kind="ramp_h"), "k_yuv444_resize")
+add("yuv_up_i444", "YUV i444", yuv444_case(capi.YUV_LIMITED, capi.BT601, False, (64, 128), tail="normalise", w=16, h=12), "k_yuv444_resize")
+add("yuv_rs_i444_crop_odd", "YUV i444", yuv444_case(capi.YUV_LIMITED, capi.BT709, False, (21, 13), crop=(5, 3, 31, 17), kind="chroma_checker"), "k_yuv444_resize")
+add("yuv_px_i444_crop_odd", "YUV i444", yuv444_case(capi.YUV_FULL, capi.BT601, True, None, crop=(11, 3, 21, 9)))
 
 _AFF = affine_matrix(17.0, 1.31, 3.37, -2.21, (60, 45))
 add("warp_affine", "warp", warp_case(cvgs.WARP_AFFINE, [_AFF], (90, 120), (110, 100)))

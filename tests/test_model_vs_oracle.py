@@ -5,7 +5,7 @@ The sensitivity tests flip each defining choice of the model in turn and assert 
 of the grid: the bound is tight enough to catch each of those mistakes.
 
 Largest |oracle - model| / tolerance per family on this grid (1 = at the bound):  K1 8u 0.36, 16u 0.38, 16s 0.34, 32f 0.47, 16f 0.34,
-16bf 0.35; YUV nv12 / nv21 / i420 / yv12 0.79, p010 0.75, yuyv / uyvy 0.80; warp 0.33 (fp32 outputs; 0.50 is the integer output's half
+16bf 0.35; YUV nv12 / nv21 / i420 / yv12 0.79, p010 0.75, yuyv / uyvy 0.80, i444 0.59; warp 0.33 (fp32 outputs; 0.50 is the integer output's half
 step); chains 0.60; stores 1.00 -- a 16-bit float output's tolerance IS one rounding of its format, which a random input reaches, so
 that figure says nothing about slack; the chain bound underneath it is the K1 / chains one.  No family sits below 0.01."""
 import ctypes as C
@@ -31,6 +31,9 @@ def oracle_output(oracle, name):
     if getattr(build, "layout422", None) is not None:
         from tests import yuv422_cases as Y
         Y.Expect(oracle, B.sources, build.layout422).run(iops)
+    elif getattr(build, "layout444", False):
+        from tests import yuv444_cases as Y444
+        Y444.Expect(oracle, B.surfs444).run(iops)
     else:
         oracle.execute(cvgs.lower(iops))
     got = B.result()
@@ -98,6 +101,7 @@ SENSITIVITY = {
     "ar_extent_truncated": ["k1_8uc3_ar", "k1_8uc3_ar_left"],
     "warp_border_replicate": ["warp_affine", "warp_persp_0"],
     "coefficient_digit_off": ["yuv_px_nv12_r0_p0_a0", "yuv_px_p010_r1_p2_a0", "yuv_px_nv12_r1_p1_a0"],
+    "i444_chroma_subsampled": ["yuv_px_i444_chroma_checker", "yuv_rs_i444_crop_odd"],
 }
 
 

@@ -1,5 +1,8 @@
 // common.h -- harness shared by the C++ facade tests (the role of the reference's tests/testsCommon.cuh):
 // result checks with the reference's tolerances, deterministic inputs, and the CPU oracle as the checker.
+// run_oracle(...) runs the oracle on the descriptor that the SAME facade lowered (fk::lowerChain): it checks the kernels against the oracle
+// UNDER the facade's own lowering, and cannot see a chain that is lowered wrongly.  What checks the lowering is facade_model.cpp, whose
+// outputs tests/test_facade_model.py and tests/test_gpu_facade_model.py hold to the independent float64 model (tests/f64_model.py).
 #pragma once
 
 #include <cvGPUSpeedup.h>

@@ -199,6 +199,7 @@ static constexpr int kInline64 = 8;
 // ---- launch entry points implemented in the .hip files -----------------------------------------
 struct LaunchInfo {
     const char* kernel; // name of the kernel variant chosen
+    int rows;           // K1 (k1_resize_split): output rows per wave of the instantiation chosen (1 / 2 / 4); 0 for every other kernel
 };
 
 // generic interpreted kernel: any valid chain

@@ -23,16 +23,18 @@
 //    by this kernel, so it should not wait in L2 for the end-of-kernel write-back.
 //  * small launches use 1 row per wave (maximum parallelism, shortest critical path), large ones 4 (amortises the
 //    column geometry).
+#include <cstdio>
+
 #include "k_k1_bf16.hpp"
 
 namespace cvgs {
 
 // the planar-tensor variants of 3- / 4-channel sources live in k_k1_c3.hip / k_k1_c4.hip (parallel compilation)
-hipError_t k1_launch_planar_c3(int src, bool f16, int prog_id, bool table, int rpw, const ChainArgs& c, const PlaneParams* ip, int ni, int out_cn, LaunchCtx& s);
-hipError_t k1_launch_planar_c4(int src, bool f16, int prog_id, bool table, int rpw, const ChainArgs& c, const PlaneParams* ip, int ni, int out_cn, LaunchCtx& s);
+hipError_t k1_launch_planar_c3(int src, bool f16, int prog_id, bool table, int rows, const ChainArgs& c, const PlaneParams* ip, int ni, int out_cn, LaunchCtx& s);
+hipError_t k1_launch_planar_c4(int src, bool f16, int prog_id, bool table, int rows, const ChainArgs& c, const PlaneParams* ip, int ni, int out_cn, LaunchCtx& s);
 // ... and the bf16 (CV_16BF) store variants of every fp16 one, in k_k1_bf16_c3.hip / k_k1_bf16_c4.hip (mode: k_k1_bf16.hpp K1Bf16Mode)
-hipError_t k1_launch_bf16_c3(int mode, int prog_id, bool canon, bool table, int rpw, const ChainArgs& c, const PlaneParams* ip, int ni, int out_cn, LaunchCtx& s);
-hipError_t k1_launch_bf16_c4(int mode, int prog_id, bool canon, bool table, int rpw, const ChainArgs& c, const PlaneParams* ip, int ni, int out_cn, LaunchCtx& s);
+hipError_t k1_launch_bf16_c3(int mode, int prog_id, bool canon, bool table, int rows, const ChainArgs& c, const PlaneParams* ip, int ni, int out_cn, LaunchCtx& s);
+hipError_t k1_launch_bf16_c4(int mode, int prog_id, bool canon, bool table, int rows, const ChainArgs& c, const PlaneParams* ip, int ni, int out_cn, LaunchCtx& s);
 
 int launch_k1(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_inline, LaunchCtx& ctx, bool dry_run, LaunchInfo* info, uint32_t chain_flags) {
     const MirrorArgs& mirrors = ctx.mirrors;
@@ -106,7 +108,7 @@ int launch_k1(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_inl
     // separate pitched planes (the K2 chain): 4 rows per wave already from 16 Ki wave-rows (session-5 sweep: 4K -> 1080p into 3 planes
     // 14.9 -> 13.3 us, 6K -> 720p 8.9 -> 8.5 us; the packed modes tie or lose there)
     if (split2d && wave_rows > 16384) rpw = 4;
-    static const char* rpw_env = getenv("CVGS_K1_RPW"); // tuning hook (benchmarks only): force 1 / 2 / 4 rows per wave
+    static const char* rpw_env = getenv("CVGS_K1_RPW"); // tuning / test hook: ask for 1 / 2 / 4 rows per wave whatever the launch size
     if (rpw_env) rpw = atoi(rpw_env) >= 4 ? 4 : (atoi(rpw_env) == 2 ? 2 : 1);
 
     const bool table = r.table != nullptr;
@@ -134,6 +136,10 @@ int launch_k1(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_inl
     }
     if (prog_id == 2 && planar_prog == 2 && !canon_packed) interp_arith_setup(c_mut.prog, r.cn);
 
+    // the rows per wave of the kernel that exists for this request (k_k1_impl.hpp: the one mapping; the launchers switch on its answer)
+    const bool interpreted = planar && (few ? (planar_prog != 1 && planar_prog != 3) : planar_prog == 2);
+    const int rows = k1_rows_instantiated(interpreted, r.depth == CVGS_DEPTH_8U, planar ? WM_PLANAR : (split2d ? WM_SPLIT2D : WM_PACKED), few, mirrors.n > 0, rpw);
+
     const int src = r.depth == CVGS_DEPTH_8U ? SRC_U8 : (r.depth == CVGS_DEPTH_16U ? SRC_U16 : (r.depth == CVGS_DEPTH_16S ? SRC_S16 : SRC_F32));
     // whole-frame resize -> cast -> packed pixels of the SOURCE's type with nothing in between (the reference's
     // tests/resize/test_resize_write.cu chain): several output pixels per lane (k_k1_x4.hip) once the launch is in the
@@ -150,7 +156,7 @@ int launch_k1(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_inl
                     {"k1_u16c1_packed_u16_x2", "", "k1_u16c3_packed_u16_x2", "k1_u16c4_packed_u16_x2"},
                     {"k1_s16c1_packed_s16_x2", "", "k1_s16c3_packed_s16_x2", "k1_s16c4_packed_s16_x2"},
                     {"k1_f32c1_packed_f32_x4", "", "", ""}};
-                if (info) info->kernel = names_x4[src][r.cn - 1];
+                if (info) info->kernel = names_x4[src][r.cn - 1], info->rows = 0; // (not k1_resize_split: no rows per wave to report)
                 return rc;
             }
         }
@@ -194,6 +200,14 @@ int launch_k1(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_inl
             info->kernel = names_canon[r.cn == 4][u8out ? 2 : (f16 ? 1 : 0)];
         } else info->kernel = names_other[r.cn == 4][split2d ? 3 : (u8out ? 2 : (f16 ? 1 : 0))];
         if (bf16) info->kernel = bf16_kernel_name(info->kernel);
+        info->rows = rows;
+        if (rpw_env) { // under the hook, and only then, the name says which row count was INSTANTIATED: "@r1" / "@r2" / "@r4" (tests/test_gpu_k1_rows.py)
+            // Every other name is a string literal; this one lives in a per-thread buffer and is valid only until the next launch_k1 call of the
+            // same thread that asks for a name.  cvgs_kernel_name (cvgs_api.cpp), the one consumer, copies it out before it returns.
+            static thread_local char hooked[96];
+            snprintf(hooked, sizeof(hooked), "%s@r%d", info->kernel, rows);
+            info->kernel = hooked;
+        }
     }
     if (dry_run) return 1;
     LaunchCtx& s = ctx;
@@ -202,8 +216,8 @@ int launch_k1(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_inl
     if (bf16) {
         const int mode = mirrors.n > 0 ? K1_BF16_MIRRORED : (planar ? K1_BF16_PLANAR : K1_BF16_PACKED);
         const int pid = mirrors.n > 0 ? prog_id : planar_prog;
-        e = r.cn == 3 ? k1_launch_bf16_c3(mode, pid, canon_packed, table, rpw, c, inline_planes, n_inline, out_cn, s)
-                      : k1_launch_bf16_c4(mode, pid, canon_packed, table, rpw, c, inline_planes, n_inline, out_cn, s);
+        e = r.cn == 3 ? k1_launch_bf16_c3(mode, pid, canon_packed, table, rows, c, inline_planes, n_inline, out_cn, s)
+                      : k1_launch_bf16_c4(mode, pid, canon_packed, table, rows, c, inline_planes, n_inline, out_cn, s);
     } else if (mirrors.n > 0) {
         // one row per wave (a 64-crop launch is in the latency regime), planes in the kernel arguments
         // fp16 tensors (the half-precision hand-off) halve the bytes every xGMI link has to carry
@@ -219,28 +233,28 @@ int launch_k1(const ChainArgs& c_in, const PlaneParams* inline_planes, int n_inl
         auto mir = [&](auto prog_tag) { return f16 ? mir_t(prog_tag, _Float16{}) : mir_t(prog_tag, float{}); };
         e = prog_id == 0 ? mir(ProgSwapMulSubDiv{}) : (prog_id == 1 ? mir(ProgMulSubDiv{}) : mir(InterpProg{}));
     } else if (same_type_packed) {
-        e = r.cn == 1 ? launch_same_type_packed<1>(src, table, rpw, c, inline_planes, n_inline, s)
-            : r.cn == 3 ? launch_same_type_packed<3>(src, table, rpw, c, inline_planes, n_inline, s)
-                        : launch_same_type_packed<4>(src, table, rpw, c, inline_planes, n_inline, s);
+        e = r.cn == 1 ? launch_same_type_packed<1>(src, table, rows, c, inline_planes, n_inline, s)
+            : r.cn == 3 ? launch_same_type_packed<3>(src, table, rows, c, inline_planes, n_inline, s)
+                        : launch_same_type_packed<4>(src, table, rows, c, inline_planes, n_inline, s);
     } else if (planes_16) {
-        e = r.cn == 3 ? launch_split2d_16<3>(src, table, rpw, c, inline_planes, n_inline, s)
-                      : launch_split2d_16<4>(src, table, rpw, c, inline_planes, n_inline, s);
+        e = r.cn == 3 ? launch_split2d_16<3>(src, table, rows, c, inline_planes, n_inline, s)
+                      : launch_split2d_16<4>(src, table, rows, c, inline_planes, n_inline, s);
     } else if (few) {
-        e = r.cn == 1 ? launch_few<1>(src, planar, u8out, planar_prog, table, rpw, c, inline_planes, n_inline, s, canon_packed)
-                      : launch_few<2>(src, planar, u8out, planar_prog, table, rpw, c, inline_planes, n_inline, s, canon_packed);
+        e = r.cn == 1 ? launch_few<1>(src, planar, u8out, planar_prog, table, rows, c, inline_planes, n_inline, s, canon_packed)
+                      : launch_few<2>(src, planar, u8out, planar_prog, table, rows, c, inline_planes, n_inline, s, canon_packed);
     } else if (!planar) {
-        if (split2d) e = r.cn == 3 ? launch_split2d<3>(prog_id, table, rpw, c, inline_planes, n_inline, s)
-                                   : launch_split2d<4>(prog_id, table, rpw, c, inline_planes, n_inline, s);
-        else if (u8out) e = r.cn == 3 ? launch_other_np<3, uint8_t, WM_PACKED>(n_prog == 0, table, rpw, c, inline_planes, n_inline, s, canon_packed)
-                                      : launch_other_np<4, uint8_t, WM_PACKED>(n_prog == 0, table, rpw, c, inline_planes, n_inline, s, canon_packed);
-        else if (f16) e = r.cn == 3 ? launch_other_np<3, _Float16, WM_PACKED>(false, table, rpw, c, inline_planes, n_inline, s, canon_packed)
-                                    : launch_other_np<4, _Float16, WM_PACKED>(false, table, rpw, c, inline_planes, n_inline, s, canon_packed);
-        else e = r.cn == 3 ? launch_other_np<3, float, WM_PACKED>(n_prog == 0, table, rpw, c, inline_planes, n_inline, s, canon_packed)
-                           : launch_other_np<4, float, WM_PACKED>(n_prog == 0, table, rpw, c, inline_planes, n_inline, s, canon_packed);
+        if (split2d) e = r.cn == 3 ? launch_split2d<3>(prog_id, table, rows, c, inline_planes, n_inline, s)
+                                   : launch_split2d<4>(prog_id, table, rows, c, inline_planes, n_inline, s);
+        else if (u8out) e = r.cn == 3 ? launch_other_np<3, uint8_t, WM_PACKED>(n_prog == 0, table, rows, c, inline_planes, n_inline, s, canon_packed)
+                                      : launch_other_np<4, uint8_t, WM_PACKED>(n_prog == 0, table, rows, c, inline_planes, n_inline, s, canon_packed);
+        else if (f16) e = r.cn == 3 ? launch_other_np<3, _Float16, WM_PACKED>(false, table, rows, c, inline_planes, n_inline, s, canon_packed)
+                                    : launch_other_np<4, _Float16, WM_PACKED>(false, table, rows, c, inline_planes, n_inline, s, canon_packed);
+        else e = r.cn == 3 ? launch_other_np<3, float, WM_PACKED>(n_prog == 0, table, rows, c, inline_planes, n_inline, s, canon_packed)
+                           : launch_other_np<4, float, WM_PACKED>(n_prog == 0, table, rows, c, inline_planes, n_inline, s, canon_packed);
     } else if (r.cn == 3) {
-        e = k1_launch_planar_c3(src, f16, planar_prog, table, rpw, c, inline_planes, n_inline, out_cn, s);
+        e = k1_launch_planar_c3(src, f16, planar_prog, table, rows, c, inline_planes, n_inline, out_cn, s);
     } else {
-        e = k1_launch_planar_c4(src, f16, planar_prog, table, rpw, c, inline_planes, n_inline, out_cn, s);
+        e = k1_launch_planar_c4(src, f16, planar_prog, table, rows, c, inline_planes, n_inline, out_cn, s);
     }
     return e == hipSuccess ? 1 : -(int)e - 1000;
 }

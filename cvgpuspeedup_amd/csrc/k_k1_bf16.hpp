@@ -12,9 +12,9 @@ enum K1Bf16Mode { K1_BF16_PLANAR = 0, K1_BF16_PACKED = 1, K1_BF16_MIRRORED = 2 }
 // PACKED: packed pixels (canon: the chain was rewritten into the canonical pipeline); MIRRORED: planar tensor + cvgs_write_desc.mirrors,
 // planes in the kernel arguments, prog_id = k1_classify_program's answer
 template <int CN>
-static hipError_t k1_launch_bf16(int mode, int prog_id, bool canon, bool table, int rpw, const ChainArgs& c, const PlaneParams* ip, int ni, int out_cn,
+static hipError_t k1_launch_bf16(int mode, int prog_id, bool canon, bool table, int rows, const ChainArgs& c, const PlaneParams* ip, int ni, int out_cn,
                                  LaunchCtx& s) {
-    if (mode == K1_BF16_PACKED) return launch_other_np<CN, __bf16, WM_PACKED>(false, table, rpw, c, ip, ni, s, canon);
+    if (mode == K1_BF16_PACKED) return launch_other_np<CN, __bf16, WM_PACKED>(false, table, rows, c, ip, ni, s, canon);
     if (mode == K1_BF16_MIRRORED) {
         auto mir = [&](auto prog_tag) {
             using Pg = decltype(prog_tag);
@@ -23,7 +23,7 @@ static hipError_t k1_launch_bf16(int mode, int prog_id, bool canon, bool table, 
         };
         return prog_id == 0 ? mir(ProgSwapMulSubDiv{}) : (prog_id == 1 ? mir(ProgMulSubDiv{}) : mir(InterpProg{}));
     }
-    return launch_prog<CN, SRC_U8, __bf16>(prog_id, table, rpw, c, ip, ni, out_cn, s);
+    return launch_prog<CN, SRC_U8, __bf16>(prog_id, table, rows, c, ip, ni, out_cn, s);
 }
 
 } // namespace cvgs

@@ -2,6 +2,35 @@
 // (k_k1.hip: the dispatcher, packed / separate-plane / 1-2 channel / mirrored variants; k_k1_c3.hip, k_k1_c4.hip: the planar-tensor
 // variants of 3- and 4-channel sources -- split only so that the ~300 instantiations compile in parallel).  See k_k1.hip.
 #pragma once
+
+// ---- rows per wave: which k1_resize_split<..., RPW, ...> a launch instantiates -----------------------------------------------------------
+// Plain host C++ without a HIP header in sight: tests/cpp/k1_rows_table.cpp includes this file with CVGS_K1_ROWS_ONLY defined and holds
+// the function to its table on the CPU.
+namespace cvgs {
+
+// Write stages of the fast path.  Planar is the hot one (TensorSplit / TensorTSplit); the other two serve the
+// single-image chains of the reference's resize tests (tests/resize/test_resize_write.cu: resize -> convertTo<32F,8U> ->
+// write; tests/resize/test_resize_x_split.cu: resize -> mul -> sub -> div -> split(vector<GpuMat>)).
+enum { WM_PLANAR = 0, WM_PACKED = 1, WM_SPLIT2D = 2 };
+
+// The ONE place that turns the rows per wave launch_k1 asks for (1 / 2 / 4: by launch size, or the CVGS_K1_RPW hook) into the row count
+// of the kernel that exists; the launchers below switch on its answer and refuse any other value.  0: no such request.
+//   interpreted: the program runs interpreted (InterpProg / InterpProgArith) -- its opcode loop stays rolled, more rows only bloat it
+//   src_u8:      8-bit sources (16-bit and fp32 ones get by with two row counts)
+//   wm:          WM_PLANAR / WM_PACKED / WM_SPLIT2D;   few: 1- / 2-channel sources;   mirrored: the launch also writes peers' tensors
+inline int k1_rows_instantiated(bool interpreted, bool src_u8, int wm, bool few, bool mirrored, int rpw) {
+    if (rpw != 1 && rpw != 2 && rpw != 4) return 0;
+    if (mirrored) return 1;                              // a 64-crop shard is in the latency regime
+    if (wm != WM_PLANAR) return rpw >= 4 ? 4 : 1;        // launch_other: packed pixels / separate planes, every program
+    if (interpreted) return 1;                           // launch_rpw / launch_few_planar
+    if (few) return rpw >= 4 ? 4 : 1;                    // launch_few_planar
+    if (!src_u8) return rpw == 1 ? 1 : 4;                // launch_rpw
+    return rpw;
+}
+
+} // namespace cvgs
+
+#ifndef CVGS_K1_ROWS_ONLY
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -14,11 +43,6 @@
 #include "k_taps.hpp"
 
 namespace cvgs {
-
-// Write stages of the fast path.  Planar is the hot one (TensorSplit / TensorTSplit); the other two serve the
-// single-image chains of the reference's resize tests (tests/resize/test_resize_write.cu: resize -> convertTo<32F,8U> ->
-// write; tests/resize/test_resize_x_split.cu: resize -> mul -> sub -> div -> split(vector<GpuMat>)).
-enum { WM_PLANAR = 0, WM_PACKED = 1, WM_SPLIT2D = 2 };
 
 // waves per workgroup (each wave owns RPW output rows of 64 columns; waves of a workgroup share nothing, so this only sets
 // the dispatch granularity).  Round-2 A/B (-DCVGS_K1_WPB=1/2/4/8): the 50-crop launch 4.48 / 4.34 / 4.40 / 4.55 us,
@@ -469,91 +493,102 @@ static hipError_t launch_t(const ChainArgs& c, const PlaneParams* inline_planes,
 }
 
 // packed / separate-plane targets; one row per wave, four for whole-frame sizes
+// (`rows` here and in every launcher below: k1_rows_instantiated's answer, the rows per wave of the kernel to launch)
 template <int CN, typename OT, int WM, class Prog = InterpProg, int SRC = SRC_U8>
-static hipError_t launch_other(bool table, int rpw, const ChainArgs& c, const PlaneParams* ip, int ni, LaunchCtx& s) {
-    if (rpw >= 4) {
+static hipError_t launch_other(bool table, int rows, const ChainArgs& c, const PlaneParams* ip, int ni, LaunchCtx& s) {
+    switch (rows) {
+    case 4:
         if (table) return launch_t<CN, 0, 4, Prog, SRC, OT, WM>(c, ip, ni, c.write.cn, s);
         return launch_t<CN, CVGS_KERNARG_PLANES, 4, Prog, SRC, OT, WM>(c, ip, ni, c.write.cn, s);
+    case 1:
+        if (table) return launch_t<CN, 0, 1, Prog, SRC, OT, WM>(c, ip, ni, c.write.cn, s);
+        return launch_t<CN, CVGS_KERNARG_PLANES, 1, Prog, SRC, OT, WM>(c, ip, ni, c.write.cn, s);
+    default: return hipErrorInvalidValue;
     }
-    if (table) return launch_t<CN, 0, 1, Prog, SRC, OT, WM>(c, ip, ni, c.write.cn, s);
-    return launch_t<CN, CVGS_KERNARG_PLANES, 1, Prog, SRC, OT, WM>(c, ip, ni, c.write.cn, s);
 }
 // the same with the program picked at run time: empty (nothing between the resize and the folded cast / the write) or interpreted
 template <int CN, typename OT, int WM, int SRC = SRC_U8>
-static hipError_t launch_other_np(bool none, bool table, int rpw, const ChainArgs& c, const PlaneParams* ip, int ni, LaunchCtx& s, bool canon = false) {
-    if (none) return launch_other<CN, OT, WM, ProgNone, SRC>(table, rpw, c, ip, ni, s);
+static hipError_t launch_other_np(bool none, bool table, int rows, const ChainArgs& c, const PlaneParams* ip, int ni, LaunchCtx& s, bool canon = false) {
+    if (none) return launch_other<CN, OT, WM, ProgNone, SRC>(table, rows, c, ip, ni, s);
     if constexpr (SRC == SRC_U8 && WM == WM_PACKED) { // (k_taps.hpp: the chain was rewritten into the canonical arithmetic pipeline)
-        if (canon) return launch_other<CN, OT, WM, K1CanonProg, SRC>(table, rpw, c, ip, ni, s);
+        if (canon) return launch_other<CN, OT, WM, K1CanonProg, SRC>(table, rows, c, ip, ni, s);
     }
-    return launch_other<CN, OT, WM, InterpProg, SRC>(table, rpw, c, ip, ni, s);
+    return launch_other<CN, OT, WM, InterpProg, SRC>(table, rows, c, ip, ni, s);
 }
 // 16-bit and CV_32F sources into packed pixels of the SOURCE's own type (the reference's single-image resize tests sweep
 // CV_16U / CV_16S C1, C3, C4 and CV_32FC1: resize -> convertTo<CV_32F, I> -> write<I>, tests/resize/test_resize_write.cu:55-56,
 // 110-123), and 16-bit sources into separate fp32 planes (tests/resize/test_resize_x_split.cu)
 template <int CN>
-static hipError_t launch_same_type_packed(int src, bool table, int rpw, const ChainArgs& c, const PlaneParams* ip, int ni, LaunchCtx& s) {
+static hipError_t launch_same_type_packed(int src, bool table, int rows, const ChainArgs& c, const PlaneParams* ip, int ni, LaunchCtx& s) {
     const bool none = c.prog.n == 0;
-    if (src == SRC_U16) return launch_other_np<CN, uint16_t, WM_PACKED, SRC_U16>(none, table, rpw, c, ip, ni, s);
-    if (src == SRC_S16) return launch_other_np<CN, int16_t, WM_PACKED, SRC_S16>(none, table, rpw, c, ip, ni, s);
-    return launch_other_np<CN, float, WM_PACKED, SRC_F32>(none, table, rpw, c, ip, ni, s);
+    if (src == SRC_U16) return launch_other_np<CN, uint16_t, WM_PACKED, SRC_U16>(none, table, rows, c, ip, ni, s);
+    if (src == SRC_S16) return launch_other_np<CN, int16_t, WM_PACKED, SRC_S16>(none, table, rows, c, ip, ni, s);
+    return launch_other_np<CN, float, WM_PACKED, SRC_F32>(none, table, rows, c, ip, ni, s);
 }
 template <int CN>
-static hipError_t launch_split2d_16(int src, bool table, int rpw, const ChainArgs& c, const PlaneParams* ip, int ni, LaunchCtx& s) {
-    if (src == SRC_U16) return launch_other<CN, float, WM_SPLIT2D, InterpProg, SRC_U16>(table, rpw, c, ip, ni, s);
-    return launch_other<CN, float, WM_SPLIT2D, InterpProg, SRC_S16>(table, rpw, c, ip, ni, s);
+static hipError_t launch_split2d_16(int src, bool table, int rows, const ChainArgs& c, const PlaneParams* ip, int ni, LaunchCtx& s) {
+    if (src == SRC_U16) return launch_other<CN, float, WM_SPLIT2D, InterpProg, SRC_U16>(table, rows, c, ip, ni, s);
+    return launch_other<CN, float, WM_SPLIT2D, InterpProg, SRC_S16>(table, rows, c, ip, ni, s);
 }
 // separate planes: the reference's K2 chain (mul, sub, div; with or without the R<->B swap) gets its compile-time program
 template <int CN>
-static hipError_t launch_split2d(int prog_id, bool table, int rpw, const ChainArgs& c, const PlaneParams* ip, int ni, LaunchCtx& s) {
-    if (prog_id == 0) return launch_other<CN, float, WM_SPLIT2D, ProgSwapMulSubDiv>(table, rpw, c, ip, ni, s);
-    if (prog_id == 1) return launch_other<CN, float, WM_SPLIT2D, ProgMulSubDiv>(table, rpw, c, ip, ni, s);
-    return launch_other<CN, float, WM_SPLIT2D>(table, rpw, c, ip, ni, s);
+static hipError_t launch_split2d(int prog_id, bool table, int rows, const ChainArgs& c, const PlaneParams* ip, int ni, LaunchCtx& s) {
+    if (prog_id == 0) return launch_other<CN, float, WM_SPLIT2D, ProgSwapMulSubDiv>(table, rows, c, ip, ni, s);
+    if (prog_id == 1) return launch_other<CN, float, WM_SPLIT2D, ProgMulSubDiv>(table, rows, c, ip, ni, s);
+    return launch_other<CN, float, WM_SPLIT2D>(table, rows, c, ip, ni, s);
 }
 
 template <int CN, int NPL, class Prog, int SRC, typename OT>
-static hipError_t launch_rpw(int rpw, const ChainArgs& c, const PlaneParams* ip, int ni, int out_cn, LaunchCtx& s) {
+static hipError_t launch_rpw(int rows, const ChainArgs& c, const PlaneParams* ip, int ni, int out_cn, LaunchCtx& s) {
     // the interpreted program keeps its opcode loop rolled; more than one row per wave only bloats it
-    if constexpr (std::is_same_v<Prog, InterpProg>) return launch_t<CN, NPL, 1, Prog, SRC, OT>(c, ip, ni, out_cn, s);
-    else if constexpr (std::is_same_v<Prog, InterpProgArith>) return launch_t<CN, NPL, 1, Prog, SRC, OT>(c, ip, ni, out_cn, s); // (2 rows per wave: 58.7 vs 50.7 us per tick)
-    else if constexpr (SRC != SRC_U8) { // 16-bit sources: two row counts are enough
-        if (rpw == 1) return launch_t<CN, NPL, 1, Prog, SRC, OT>(c, ip, ni, out_cn, s);
-        return launch_t<CN, NPL, 4, Prog, SRC, OT>(c, ip, ni, out_cn, s);
+    // (InterpProgArith at 2 rows per wave: 58.7 vs 50.7 us per tick)
+    if constexpr (std::is_same_v<Prog, InterpProg> || std::is_same_v<Prog, InterpProgArith>) {
+        if (rows != 1) return hipErrorInvalidValue;
+        return launch_t<CN, NPL, 1, Prog, SRC, OT>(c, ip, ni, out_cn, s);
+    } else if constexpr (SRC != SRC_U8) { // 16-bit sources: two row counts are enough
+        switch (rows) {
+        case 1: return launch_t<CN, NPL, 1, Prog, SRC, OT>(c, ip, ni, out_cn, s);
+        case 4: return launch_t<CN, NPL, 4, Prog, SRC, OT>(c, ip, ni, out_cn, s);
+        default: return hipErrorInvalidValue;
+        }
     } else
-    switch (rpw) {
+    switch (rows) {
     case 1: return launch_t<CN, NPL, 1, Prog, SRC, OT>(c, ip, ni, out_cn, s);
     case 2: return launch_t<CN, NPL, 2, Prog, SRC, OT>(c, ip, ni, out_cn, s);
-    default: return launch_t<CN, NPL, 4, Prog, SRC, OT>(c, ip, ni, out_cn, s);
+    case 4: return launch_t<CN, NPL, 4, Prog, SRC, OT>(c, ip, ni, out_cn, s);
+    default: return hipErrorInvalidValue;
     }
 }
 
 template <int CN, class Prog, int SRC, typename OT>
-static hipError_t launch_npl(bool table, int rpw, const ChainArgs& c, const PlaneParams* ip, int ni, int out_cn,
+static hipError_t launch_npl(bool table, int rows, const ChainArgs& c, const PlaneParams* ip, int ni, int out_cn,
                              LaunchCtx& s) {
-    if (table) return launch_rpw<CN, 0, Prog, SRC, OT>(rpw, c, ip, ni, out_cn, s);
+    if (table) return launch_rpw<CN, 0, Prog, SRC, OT>(rows, c, ip, ni, out_cn, s);
     if constexpr (SRC == SRC_U8) { // cvgs_execute_many on host descriptors (u8 sources, 3 / 4 channels): segments + ALL planes in the arguments
         if (s.segs) {
-            if (ni <= kManyInlineSmall) return launch_rpw<CN, -kManyInlineSmall, Prog, SRC, OT>(rpw, c, ip, ni, out_cn, s);
-            return launch_rpw<CN, -kManyInlineLarge, Prog, SRC, OT>(rpw, c, ip, ni, out_cn, s);
+            if (ni <= kManyInlineSmall) return launch_rpw<CN, -kManyInlineSmall, Prog, SRC, OT>(rows, c, ip, ni, out_cn, s);
+            return launch_rpw<CN, -kManyInlineLarge, Prog, SRC, OT>(rows, c, ip, ni, out_cn, s);
         }
     }
-    if (ni > CVGS_KERNARG_PLANES) return launch_rpw<CN, kKernargPlanesBig, Prog, SRC, OT>(rpw, c, ip, ni, out_cn, s); // 16 KB argument block
-    return launch_rpw<CN, CVGS_KERNARG_PLANES, Prog, SRC, OT>(rpw, c, ip, ni, out_cn, s);
+    if (ni > CVGS_KERNARG_PLANES) return launch_rpw<CN, kKernargPlanesBig, Prog, SRC, OT>(rows, c, ip, ni, out_cn, s); // 16 KB argument block
+    return launch_rpw<CN, CVGS_KERNARG_PLANES, Prog, SRC, OT>(rows, c, ip, ni, out_cn, s);
 }
 
 template <int CN, int SRC, typename OT = float>
-static hipError_t launch_prog(int prog_id, bool table, int rpw, const ChainArgs& c, const PlaneParams* ip, int ni, int out_cn,
+static hipError_t launch_prog(int prog_id, bool table, int rows, const ChainArgs& c, const PlaneParams* ip, int ni, int out_cn,
                               LaunchCtx& s) {
-    if (prog_id == 0) return launch_npl<CN, ProgSwapMulSubDiv, SRC, OT>(table, rpw, c, ip, ni, out_cn, s);
-    if (prog_id == 1) return launch_npl<CN, ProgMulSubDiv, SRC, OT>(table, rpw, c, ip, ni, out_cn, s);
-    if (prog_id == 3) return launch_npl<CN, K1CanonProg, SRC, OT>(table, rpw, c, ip, ni, out_cn, s); // (k_taps.hpp: the canonical arithmetic pipeline)
-    return launch_npl<CN, InterpProgArith, SRC, OT>(table, rpw, c, ip, ni, out_cn, s);
+    if (prog_id == 0) return launch_npl<CN, ProgSwapMulSubDiv, SRC, OT>(table, rows, c, ip, ni, out_cn, s);
+    if (prog_id == 1) return launch_npl<CN, ProgMulSubDiv, SRC, OT>(table, rows, c, ip, ni, out_cn, s);
+    if (prog_id == 3) return launch_npl<CN, K1CanonProg, SRC, OT>(table, rows, c, ip, ni, out_cn, s); // (k_taps.hpp: the canonical arithmetic pipeline)
+    return launch_npl<CN, InterpProgArith, SRC, OT>(table, rows, c, ip, ni, out_cn, s);
 }
 
 // 1- and 2-channel sources (grayscale / two-plane images; the reference's single-image resize tests sweep C1 types,
 // tests/resize/test_resize_write.cu:120-123): planar fp32 for every source kind, packed fp32 / u8 for 8U sources
 template <int CN, int SRC>
-static hipError_t launch_few_planar(int prog_id, bool table, int rpw, const ChainArgs& c, const PlaneParams* ip, int ni, LaunchCtx& s) {
-    const int r = rpw >= 4 ? 4 : 1;
+static hipError_t launch_few_planar(int prog_id, bool table, int rows, const ChainArgs& c, const PlaneParams* ip, int ni, LaunchCtx& s) {
+    const int r = rows;
+    if (r != 1 && r != 4) return hipErrorInvalidValue;
     if constexpr (SRC == SRC_U8) {
         if (prog_id == 3) { // the canonical arithmetic pipeline (k_taps.hpp)
             if (table) return r == 4 ? launch_t<CN, 0, 4, K1CanonProg, SRC, float>(c, ip, ni, CN, s) : launch_t<CN, 0, 1, K1CanonProg, SRC, float>(c, ip, ni, CN, s);
@@ -566,21 +601,23 @@ static hipError_t launch_few_planar(int prog_id, bool table, int rpw, const Chai
         return r == 4 ? launch_t<CN, CVGS_KERNARG_PLANES, 4, ProgMulSubDiv, SRC, float>(c, ip, ni, CN, s)
                       : launch_t<CN, CVGS_KERNARG_PLANES, 1, ProgMulSubDiv, SRC, float>(c, ip, ni, CN, s);
     }
+    if (r != 1) return hipErrorInvalidValue; // (the interpreted program: one row per wave)
     if (table) return launch_t<CN, 0, 1, InterpProg, SRC, float>(c, ip, ni, CN, s);
     return launch_t<CN, CVGS_KERNARG_PLANES, 1, InterpProg, SRC, float>(c, ip, ni, CN, s);
 }
 template <int CN>
-static hipError_t launch_few(int src, bool planar, bool u8out, int prog_id, bool table, int rpw, const ChainArgs& c, const PlaneParams* ip,
+static hipError_t launch_few(int src, bool planar, bool u8out, int prog_id, bool table, int rows, const ChainArgs& c, const PlaneParams* ip,
                              int ni, LaunchCtx& s, bool canon = false) {
     if (planar) {
-        return src == SRC_U8    ? launch_few_planar<CN, SRC_U8>(prog_id, table, rpw, c, ip, ni, s)
-               : src == SRC_U16 ? launch_few_planar<CN, SRC_U16>(prog_id, table, rpw, c, ip, ni, s)
-               : src == SRC_S16 ? launch_few_planar<CN, SRC_S16>(prog_id, table, rpw, c, ip, ni, s)
-                                : launch_few_planar<CN, SRC_F32>(prog_id, table, rpw, c, ip, ni, s);
+        return src == SRC_U8    ? launch_few_planar<CN, SRC_U8>(prog_id, table, rows, c, ip, ni, s)
+               : src == SRC_U16 ? launch_few_planar<CN, SRC_U16>(prog_id, table, rows, c, ip, ni, s)
+               : src == SRC_S16 ? launch_few_planar<CN, SRC_S16>(prog_id, table, rows, c, ip, ni, s)
+                                : launch_few_planar<CN, SRC_F32>(prog_id, table, rows, c, ip, ni, s);
     }
-    if (u8out) return launch_other_np<CN, uint8_t, WM_PACKED>(c.prog.n == 0, table, rpw, c, ip, ni, s, canon);
-    return launch_other_np<CN, float, WM_PACKED>(c.prog.n == 0, table, rpw, c, ip, ni, s, canon);
+    if (u8out) return launch_other_np<CN, uint8_t, WM_PACKED>(c.prog.n == 0, table, rows, c, ip, ni, s, canon);
+    return launch_other_np<CN, float, WM_PACKED>(c.prog.n == 0, table, rows, c, ip, ni, s, canon);
 }
 
 
 } // namespace cvgs
+#endif // CVGS_K1_ROWS_ONLY

@@ -174,7 +174,15 @@ def normalise(cn, swap=True):
                   cvgs.divide(f, H.K1_DIV[cn] if cn in H.K1_DIV else [0.25] * cn)]
 
 
-def resize_case(depth, cn, frame_hw, crops, dst, ar=cvgs.IGNORE_AR, used=None, tail="none", write="split", seed=1, out16=None):
+ARITH_MUL, ARITH_ADD = [0.9, 0.8, 0.7, 0.6], [3.5, 2.25, 1.75, 0.5]  # tail="arith": stays inside 0..255 on u8 sources (integer outputs do not saturate flat)
+
+
+def resize_case(depth, cn, frame_hw, crops, dst, ar=cvgs.IGNORE_AR, used=None, tail="none", write="split", seed=1, out16=None, out_int=None, table=False,
+                pitch_pad=3):
+    """tail: none | normalise (swap, x, -, /) | mul_sub_div (x, -, /) | arith (x, +) | interp (x, +, -, x, /: no canonical form).
+    write: split | splitT | packed | planes2d (separate pitched fp32 planes, pitch_pad elements wider than the target).
+    out_int: a packed integer output of that depth (the saturating cast folds into the store).  table: on a device backend the planes
+    travel as a resident device table (cvgs_plane_table_build) instead of in the kernel arguments."""
     def build(B):
         st = src_type(depth, cn)
         frame = random_src((frame_hw[0], frame_hw[1], cn), depth, seed)
@@ -183,17 +191,39 @@ def resize_case(depth, cn, frame_hw, crops, dst, ar=cvgs.IGNORE_AR, used=None, t
         f = cvgs.make_type(cvgs.CV_32F, cn)
         n = len(crops)
         rd = cvgs.resize(B.T(st), cvgs.INTER_LINEAR, [m.roi(*c) for c in crops], dst, n if used is None else used, BG[:cn], ar)
-        ops = normalise(cn) if tail == "normalise" else []
+        if table and B.device:
+            import torch
+            t = torch.frombuffer(bytearray(cvgs.build_plane_table(rd)), dtype=torch.uint8).cuda()
+            B.keep.append(t)
+            rd.table = t.data_ptr()
+        if tail == "normalise":
+            ops = normalise(cn)
+        elif tail == "mul_sub_div":
+            ops = normalise(cn, swap=False)
+        elif tail == "arith":
+            ops = [cvgs.multiply(f, ARITH_MUL[:cn]), cvgs.add(f, ARITH_ADD[:cn])]
+        elif tail == "interp":
+            ops = [cvgs.multiply(f, ARITH_MUL[:cn]), cvgs.add(f, ARITH_ADD[:cn]), cvgs.subtract(f, [0.4] * cn), cvgs.multiply(f, [1.25] * cn), cvgs.divide(f, [0.25] * cn)]
+        else:
+            assert tail == "none", tail
+            ops = []
         ot = f
         if out16 is not None:
             ot = src_type(out16, cn)
             ops += B.to16(f, ot)
+        if out_int is not None:
+            ot = cvgs.make_type(out_int, cn)
+            ops += [cvgs.convertTo(f, ot)]
         o1 = cvgs.make_type(capi.type_depth(ot), 1) | (ot & capi.TYPE_FLAG_BF16)
         if write == "split":
             wr = cvgs.split(B.T(ot), B.out((n, cn * dst[0] * dst[1]), o1), dst)
         elif write == "splitT":
             o = B.out((n, cn * dst[0] * dst[1]), o1)
             wr = cvgs.splitT(B.T(ot), o.data, dst[0], dst[1], n, keep=o)
+        elif write == "planes2d":
+            o = B.out((n * cn * dst[1], dst[0] + pitch_pad), cvgs.CV_32FC1)
+            planes = [[cvgs.GpuMat(dst[1], dst[0], cvgs.CV_32FC1, o.data + ((z * cn + k) * dst[1]) * o.step, o.step, owner=o) for k in range(cn)] for z in range(n)]
+            wr = cvgs.split(f, planes if n > 1 else planes[0])
         else:
             wr = cvgs.write(B.T(ot), B.out((n, dst[0] * dst[1], cn), ot), dst)
         return [rd] + ops + [wr], [F.View(frame, *c) for c in crops]

@@ -20,16 +20,10 @@ typedef uint64_t u64_unaligned __attribute__((aligned(1)));
 typedef const __attribute__((address_space(1))) u64_unaligned* gptr_u64;
 
 struct N12Geom : YuvFamGeom {}; // (a type of its own: part of the kernels' signature)
-template <int NPL> using K4Args = YuvFamArgs<NPL>;
 
-// waves per workgroup (see k_k1.hip): an A/B build may override it
-#ifndef CVGS_K4_WPB
-#define CVGS_K4_WPB 4
-#endif
-constexpr int kK4Waves = CVGS_K4_WPB;
-constexpr int kK4TileRow = 80; // floats between the rows of a wave's LDS tile (64 + padding: the 16-byte reads of a row group do not collide)
-
-// RPW output rows per wave (the launcher uses 1, see launch_yuv_fam_rows); CN output channels (3, or 4 with alpha).  One tap's conversion:
+// The prologue, the store stage, the window machinery, the blend and the LDS epilogue below stand a second and a third time in
+// k_yuv422.hip and k_yuv444.hip, and a fix to one belongs in all three: writing them once changes the machine code.
+// RPW output rows per wave (the launcher uses 1 or 4, see launch_yuv_fam_rows); CN output channels (3, or 4 with alpha).  One tap's conversion:
 // k4_tap (k_common.hpp), shared with the descriptor queue's NV12 worker (k_queue.hip).
 // S16: P010 -- the same geometry with 16-bit samples (10-bit code = sample >> 6): the two luma taps are ONE 4-byte load, the
 // two chroma pairs ONE 8-byte load.
@@ -41,7 +35,7 @@ constexpr int kK4TileRow = 80; // floats between the rows of a wave's LDS tile (
 // plane.  The two chroma taps of a plane are ONE unaligned 2-byte load per source row (6 loads per pixel instead of 4); the
 // (U,V) pairs are then assembled in registers and everything downstream is the NV12 arithmetic, bit for bit.
 template <int NPL, class Prog, typename OT = float, int RPW = 1, int CN = 3, bool S16 = false, bool WIN = false, bool PL = false>
-__global__ __launch_bounds__(64 * kK4Waves) void k4_nv12_resize(const K4Args<NPL> a, const N12Geom g) {
+__global__ __launch_bounds__(64 * kYuvFamWaves) void k4_nv12_resize(const YuvFamArgs<NPL> a, const N12Geom g) {
     const ChainArgs& c = a.c;
     const int dst_w = g.dst_w, dst_h = g.dst_h, W = g.out_w;
     PlaneParams P;
@@ -90,7 +84,7 @@ __global__ __launch_bounds__(64 * kK4Waves) void k4_nv12_resize(const K4Args<NPL
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = (int)(threadIdx.x & 63);
     const int x = col_tile * 64 + lane;
-    const int row0 = (row_group * kK4Waves + wave) * RPW;
+    const int row0 = (row_group * kYuvFamWaves + wave) * RPW;
     if (row0 >= dst_h || x >= dst_w) return;
 
     // one output pixel of row y (wave-uniform row pointers; planar: non-temporal rows, packed: the generic write stage)
@@ -129,16 +123,6 @@ __global__ __launch_bounds__(64 * kK4Waves) void k4_nv12_resize(const K4Args<NPL
         const uint32_t xb = (uint32_t)x * (uint32_t)sizeof(OT);
         OT* const orow = (OT*)out_base + (int64_t)z * img_stride + (int64_t)y * W;
 #pragma unroll
-#ifdef CVGS_K4_PLAIN_PTR
-        for (int k = 0; k < 4; ++k)
-            if (k < cn) __builtin_nontemporal_store((OT)p.v[k], orow + (int64_t)k * ch_stride + x);
-        if (g.out2) {
-            OT* const orow2 = (OT*)g.out2 + (int64_t)z * g.img_stride2 + (int64_t)y * W;
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < cn) __builtin_nontemporal_store((OT)p.v[k], orow2 + (int64_t)k * g.ch_stride2 + x);
-        }
-#else
         for (int k = 0; k < 4; ++k)
             if (k < cn) st_row(orow + (int64_t)k * ch_stride, xb, p.v[k]);
         if (g.out2) { // wave-uniform
@@ -147,7 +131,6 @@ __global__ __launch_bounds__(64 * kK4Waves) void k4_nv12_resize(const K4Args<NPL
             for (int k = 0; k < 4; ++k)
                 if (k < cn) st_row(orow2 + (int64_t)k * g.ch_stride2, xb, p.v[k]);
         }
-#endif
     }
     };
     // does the source cover the whole target?  (always, except aspect-ratio padding -- letterboxed detector inputs -- and planes
@@ -232,22 +215,17 @@ __global__ __launch_bounds__(64 * kK4Waves) void k4_nv12_resize(const K4Args<NPL
         wya[j] = (float)y2 - sy;
         wyb[j] = sy - (float)y1;
         const int r1 = __builtin_amdgcn_readfirstlane(y1), r2 = __builtin_amdgcn_readfirstlane(y2r);
-#ifdef CVGS_K4_PLAIN_PTR
-#define K4_PIN(p) (p)
-#else
-#define K4_PIN(p) pin_uniform(p)
-#endif
-        const gptr_u8 ya = K4_PIN(base + (size_t)r1 * step);
-        const gptr_u8 yb = K4_PIN(base + (size_t)r2 * step);
-        const gptr_u8 ua = K4_PIN(uvp + (size_t)(r1 >> 1) * cstep);
+        const gptr_u8 ya = pin_uniform(base + (size_t)r1 * step);
+        const gptr_u8 yb = pin_uniform(base + (size_t)r2 * step);
+        const gptr_u8 ua = pin_uniform(uvp + (size_t)(r1 >> 1) * cstep);
         if constexpr (PL) {
-            const gptr_u8 ub = K4_PIN(uvp + (size_t)(r2 >> 1) * cstep);
+            const gptr_u8 ub = pin_uniform(uvp + (size_t)(r2 >> 1) * cstep);
             vya[j] = *(gptr_u16)(ya + yo);
             vyb[j] = *(gptr_u16)(yb + yo);
             vua[j] = *(gptr_u16)(ua + uo);
             vub[j] = *(gptr_u16)(ub + uo);
-            vva[j] = *(gptr_u16)(K4_PIN(ua + plane2) + uo);
-            vvb[j] = *(gptr_u16)(K4_PIN(ub + plane2) + uo);
+            vva[j] = *(gptr_u16)(pin_uniform(ua + plane2) + uo);
+            vvb[j] = *(gptr_u16)(pin_uniform(ub + plane2) + uo);
             continue;
         }
         if constexpr (S16) {
@@ -260,18 +238,11 @@ __global__ __launch_bounds__(64 * kK4Waves) void k4_nv12_resize(const K4Args<NPL
             vua[j] = *(gptr_u32)(ua + uo);
         }
         // Every other row pair shares ONE chroma row; skipping its second load behind a wave-uniform branch was measured
-        // and lost (tools/k4_ab.sh: cfg #3 9.15 vs 8.02 us, 50 NV12 crops 5.04 vs 4.52 us): the redundant load hits L1,
+        // and lost (cfg #3 9.15 vs 8.02 us, 50 NV12 crops 5.04 vs 4.52 us): the redundant load hits L1,
         // the branch delays the loads behind it.
-#ifdef CVGS_K4_UVSKIP
-        if ((r1 >> 1) == (r2 >> 1)) {
-            vub[j] = vua[j];
-        } else
-#endif
-        {
-            const gptr_u8 ub = K4_PIN(uvp + (size_t)(r2 >> 1) * step);
-            if constexpr (S16) vub[j] = *(gptr_u64)(ub + uo);
-            else vub[j] = *(gptr_u32)(ub + uo);
-        }
+        const gptr_u8 ub = pin_uniform(uvp + (size_t)(r2 >> 1) * step);
+        if constexpr (S16) vub[j] = *(gptr_u64)(ub + uo);
+        else vub[j] = *(gptr_u32)(ub + uo);
     }
 
 #pragma unroll
@@ -364,12 +335,12 @@ __global__ __launch_bounds__(64 * kK4Waves) void k4_nv12_resize(const K4Args<NPL
             // l / 16 -- 16 bytes per lane and store instruction, three stores for the wave's four rows instead of twelve (the descriptor
             // queue's row workers publish their rows this way, k_queue.hip: q_lds_put / q_lds_get; fused launches of 4:2:0 crops are bound by
             // the number of memory instructions: four tap loads per row and lane)
-            __shared__ __attribute__((aligned(16))) float tiles[kK4Waves][CN * RPW * kK4TileRow];
+            __shared__ __attribute__((aligned(16))) float tiles[kYuvFamWaves][CN * RPW * kYuvFamTileRow];
             float* const tile = tiles[wave];
 #pragma unroll
             for (int k = 0; k < CN; ++k)
 #pragma unroll
-                for (int j = 0; j < RPW; ++j) tile[(k * RPW + j) * kK4TileRow + lane] = tv[j][k];
+                for (int j = 0; j < RPW; ++j) tile[(k * RPW + j) * kYuvFamTileRow + lane] = tv[j][k];
             __builtin_amdgcn_wave_barrier(); // (compiler ordering only: one wave's LDS operations run in order)
             typedef float f32x4t __attribute__((ext_vector_type(4)));
             typedef f32x4t f32x4t_a4 __attribute__((aligned(4)));
@@ -378,7 +349,7 @@ __global__ __launch_bounds__(64 * kK4Waves) void k4_nv12_resize(const K4Args<NPL
             float* const orow = (float*)out_base + (int64_t)z * img_stride + (int64_t)(row0 + i) * W + col_tile * 64 + q * 4;
 #pragma unroll
             for (int k = 0; k < CN; ++k) {
-                const f32x4t o = *(const f32x4t*)(tile + (k * RPW + i) * kK4TileRow + q * 4);
+                const f32x4t o = *(const f32x4t*)(tile + (k * RPW + i) * kYuvFamTileRow + q * 4);
                 __builtin_nontemporal_store(o, (gf4)(orow + (int64_t)k * ch_stride));
             }
         }
@@ -387,7 +358,6 @@ __global__ __launch_bounds__(64 * kK4Waves) void k4_nv12_resize(const K4Args<NPL
 
 // the family's traits for the shared launcher (k_yuv_family.hpp): one family per kernel variant -- interleaved 8-bit chroma (NV12 / NV21),
 // S16 (P010), PL (I420 / YV12) --, picked from the layout by k4_pick
-static_assert(kK4Waves == kYuvFamWaves, "the shared launcher sizes K4's block and grid with kYuvFamWaves: a CVGS_K4_WPB build needs its own");
 hipError_t k4_launch_bf16(int prog, const ChainArgs& c, const PlaneParams* ip, int ni, const YuvFamGeom& g, const YuvFamMany& s, bool win);
 struct K4FamilyBase : YuvFamDefaults {
     using Geom = N12Geom;

@@ -19,16 +19,15 @@ typedef const __attribute__((address_space(1))) y422_u32x2_a4* gptr_pair2; // tw
 typedef const __attribute__((address_space(1))) uint32_t* gptr_pair1;      // one pixel pair
 
 // the geometry block, the argument-block forms (NPL > 0 / == 0 / < 0) and the launcher are the YUV families' common ones (k_yuv_family.hpp)
-struct Y422Geom : YuvFamGeom {};
-template <int NPL> using Y422Args = YuvFamArgs<NPL>;
-constexpr int kY422Waves = kYuvFamWaves;
-constexpr int kY422TileRow = kYuvFamTileRow;
+struct Y422Geom : YuvFamGeom {}; // (a type of its own: part of the kernels' signature)
 
 // RPW output rows per wave; CN output channels (3, or 4 with alpha).  WIN: the target may hold an aspect-ratio window and default-value
 // planes (usedPlanes < BATCH) -- K1's / K4's machinery: the background value runs through the program once, pixels outside the window
 // take it; a separate instantiation, so that stretch-only launches do not pay for the selects.
+// All but the tap fetch stands in k_nv12.hip and in the other 4:x:x file as well, and a fix to one belongs in all three: writing it once
+// changes the machine code.
 template <int NPL, class Prog, typename OT = float, int RPW = 1, int CN = 3, bool WIN = false>
-__global__ __launch_bounds__(64 * kY422Waves) void k_yuv422_resize(const Y422Args<NPL> a, const Y422Geom g) {
+__global__ __launch_bounds__(64 * kYuvFamWaves) void k_yuv422_resize(const YuvFamArgs<NPL> a, const Y422Geom g) {
     const ChainArgs& c = a.c;
     const int dst_w = g.dst_w, dst_h = g.dst_h, W = g.out_w;
     PlaneParams P;
@@ -77,7 +76,7 @@ __global__ __launch_bounds__(64 * kY422Waves) void k_yuv422_resize(const Y422Arg
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = (int)(threadIdx.x & 63);
     const int x = col_tile * 64 + lane;
-    const int row0 = (row_group * kY422Waves + wave) * RPW;
+    const int row0 = (row_group * kYuvFamWaves + wave) * RPW;
     if (row0 >= dst_h || x >= dst_w) return;
 
     // one output pixel of row y (wave-uniform row pointers; planar: non-temporal rows, packed: one store per pixel / a coalesced u8 tile)
@@ -257,12 +256,12 @@ __global__ __launch_bounds__(64 * kY422Waves) void k_yuv422_resize(const Y422Arg
         if (tile_rows) {
             // the lane = column register layout transposed through a wave-private LDS tile: lane l then owns 4 consecutive columns of row
             // l / 16 -- 16 bytes per lane and store instruction, three stores for the wave's four rows instead of twelve (as K4)
-            __shared__ __attribute__((aligned(16))) float tiles[kY422Waves][CN * RPW * kY422TileRow];
+            __shared__ __attribute__((aligned(16))) float tiles[kYuvFamWaves][CN * RPW * kYuvFamTileRow];
             float* const tile = tiles[wave];
 #pragma unroll
             for (int k = 0; k < CN; ++k)
 #pragma unroll
-                for (int j = 0; j < RPW; ++j) tile[(k * RPW + j) * kY422TileRow + lane] = tv[j][k];
+                for (int j = 0; j < RPW; ++j) tile[(k * RPW + j) * kYuvFamTileRow + lane] = tv[j][k];
             __builtin_amdgcn_wave_barrier(); // (compiler ordering only: one wave's LDS operations run in order)
             typedef float f32x4t __attribute__((ext_vector_type(4)));
             typedef f32x4t f32x4t_a4 __attribute__((aligned(4)));
@@ -271,7 +270,7 @@ __global__ __launch_bounds__(64 * kY422Waves) void k_yuv422_resize(const Y422Arg
             float* const orow = (float*)out_base + (int64_t)z * img_stride + (int64_t)(row0 + i) * W + col_tile * 64 + q * 4;
 #pragma unroll
             for (int k = 0; k < CN; ++k) {
-                const f32x4t o = *(const f32x4t*)(tile + (k * RPW + i) * kY422TileRow + q * 4);
+                const f32x4t o = *(const f32x4t*)(tile + (k * RPW + i) * kYuvFamTileRow + q * 4);
                 __builtin_nontemporal_store(o, (gf4)(orow + (int64_t)k * ch_stride));
             }
         }

@@ -17,14 +17,13 @@ namespace cvgs {
 typedef uint16_t y444_u16u __attribute__((aligned(1)));
 typedef const __attribute__((address_space(1))) y444_u16u* gptr_tap2; // both horizontal taps of one source row of one plane
 
-constexpr int kY444Waves = kYuvFamWaves;
-constexpr int kY444TileRow = kYuvFamTileRow;
-
 // RPW output rows per wave; CN output channels (3, or 4 with alpha).  WIN: the target may hold an aspect-ratio window and default-value
 // planes (usedPlanes < BATCH) -- K1's / K4's machinery: the background value runs through the program once, pixels outside the window
 // take it; a separate instantiation, so that stretch-only launches do not pay for the selects.
+// All but the tap fetch stands in k_nv12.hip and in the other 4:x:x file as well, and a fix to one belongs in all three: writing it once
+// changes the machine code.
 template <int NPL, class Prog, typename OT = float, int RPW = 1, int CN = 3, bool WIN = false>
-__global__ __launch_bounds__(64 * kY444Waves) void k_yuv444_resize(const YuvFamArgs<NPL> a, const YuvFamGeom g) {
+__global__ __launch_bounds__(64 * kYuvFamWaves) void k_yuv444_resize(const YuvFamArgs<NPL> a, const YuvFamGeom g) {
     const ChainArgs& c = a.c;
     const int dst_w = g.dst_w, dst_h = g.dst_h, W = g.out_w;
     PlaneParams P;
@@ -72,7 +71,7 @@ __global__ __launch_bounds__(64 * kY444Waves) void k_yuv444_resize(const YuvFamA
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = (int)(threadIdx.x & 63);
     const int x = col_tile * 64 + lane;
-    const int row0 = (row_group * kY444Waves + wave) * RPW;
+    const int row0 = (row_group * kYuvFamWaves + wave) * RPW;
     if (row0 >= dst_h || x >= dst_w) return;
 
     // one output pixel of row y (wave-uniform row pointers; planar: non-temporal rows, packed: one store per pixel / a coalesced u8 tile)
@@ -252,12 +251,12 @@ __global__ __launch_bounds__(64 * kY444Waves) void k_yuv444_resize(const YuvFamA
         if (tile_rows) {
             // the lane = column register layout transposed through a wave-private LDS tile: lane l then owns 4 consecutive columns of row
             // l / 16 -- 16 bytes per lane and store instruction, three stores for the wave's four rows instead of twelve (as K4)
-            __shared__ __attribute__((aligned(16))) float tiles[kY444Waves][CN * RPW * kY444TileRow];
+            __shared__ __attribute__((aligned(16))) float tiles[kYuvFamWaves][CN * RPW * kYuvFamTileRow];
             float* const tile = tiles[wave];
 #pragma unroll
             for (int k = 0; k < CN; ++k)
 #pragma unroll
-                for (int j = 0; j < RPW; ++j) tile[(k * RPW + j) * kY444TileRow + lane] = tv[j][k];
+                for (int j = 0; j < RPW; ++j) tile[(k * RPW + j) * kYuvFamTileRow + lane] = tv[j][k];
             __builtin_amdgcn_wave_barrier(); // (compiler ordering only: one wave's LDS operations run in order)
             typedef float f32x4t __attribute__((ext_vector_type(4)));
             typedef f32x4t f32x4t_a4 __attribute__((aligned(4)));
@@ -266,7 +265,7 @@ __global__ __launch_bounds__(64 * kY444Waves) void k_yuv444_resize(const YuvFamA
             float* const orow = (float*)out_base + (int64_t)z * img_stride + (int64_t)(row0 + i) * W + col_tile * 64 + q * 4;
 #pragma unroll
             for (int k = 0; k < CN; ++k) {
-                const f32x4t o = *(const f32x4t*)(tile + (k * RPW + i) * kY444TileRow + q * 4);
+                const f32x4t o = *(const f32x4t*)(tile + (k * RPW + i) * kYuvFamTileRow + q * 4);
                 __builtin_nontemporal_store(o, (gf4)(orow + (int64_t)k * ch_stride));
             }
         }

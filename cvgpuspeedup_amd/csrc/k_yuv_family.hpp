@@ -49,7 +49,7 @@ struct YuvFamGeom {
 template <int NPL> using YuvFamArgs = std::conditional_t<NPL == 0, KernArgsMany, std::conditional_t<(NPL < 0), KernArgsManyInline<(NPL < 0 ? -NPL : 1)>, KernArgs<(NPL > 0 ? NPL : 1)>>>;
 
 constexpr int kYuvFamWaves = 4;
-constexpr int kYuvFamTileRow = 80; // floats between the rows of a wave's LDS tile (64 + padding, as K4's)
+constexpr int kYuvFamTileRow = 80; // floats between the rows of a wave's LDS tile (64 + padding: the 16-byte reads of a row group do not collide)
 
 // what the launcher hands to the instantiation it picks: the call's LaunchCtx and the chains of a cvgs_execute_many launch
 struct YuvFamMany {

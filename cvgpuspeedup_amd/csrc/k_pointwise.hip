@@ -273,6 +273,15 @@ static int launch_pointwise_u8u8(const ChainArgs& c, const PlaneParams* ip, int 
         const int rc = launch_u8_colour16(c, ip, ni, g, s, dry_run, info);
         if (rc) return rc;
     }
+    // ADD_ALPHA on a CV_8U value with an operand that is no CV_8U value (300, -1, 255.5): the result has no defined value, but it must not depend
+    // on the path.  This kernel's body stores through a saturating conversion, its tail and the generic kernel through a plain one: such
+    // chains stay on the generic kernel, so that every path gives the same bytes (tests/colour_cases.py)
+    for (int k = 0, depth = CVGS_DEPTH_8U; k < c.prog.n; ++k) {
+        if (c.prog.opcode[k] == CVGS_OP_CAST || c.prog.opcode[k] == CVGS_OP_CAST_TRUNC) depth = c.prog.aux[k];
+        if (c.prog.opcode[k] != CVGS_OP_ADD_ALPHA || depth != CVGS_DEPTH_8U) continue;
+        const float av = c.prog.operand[k][0];
+        if (!(av >= 0.f && av <= 255.f) || av != (float)(int)av) return 0;
+    }
     if (info) info->kernel = "pointwise4_u8_u8_interp";
     if (dry_run) return 1;
     hipError_t e;

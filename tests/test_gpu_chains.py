@@ -681,23 +681,7 @@ def test_u8_gray_every_rgb_triple(oracle, name, code):
     H.assert_bit_exact(out_t.cpu().numpy(), ref, "%s over all 2^24 triples" % name)
 
 
-def test_u8_colour_conversion_of_an_unaligned_crop_stays_interpreted(oracle):
-    import torch
-    dev = torch.device("cuda:0")
-    frame = H.random_u8((64, 200, 3), seed=17)
-    ft = torch.from_numpy(frame).to(dev)
-    out_t = torch.zeros((32, 64, 3), dtype=torch.uint8, device=dev)
-    ref = np.zeros((32, 64, 3), np.uint8)
-
-    def chain(m, out):
-        return [cvgs.ReadIOp(capi.READ_PIXEL, cvgs.CV_8UC3, [m.roi(3, 5, 64, 32)], 1), cvgs.cvtColor(cvgs.COLOR_BGR2RGB, cvgs.CV_8UC3), cvgs.write(cvgs.CV_8UC3, out)]
-
-    g_ops = chain(cvgs.GpuMat.from_tensor(ft, cvgs.CV_8UC3), cvgs.GpuMat.from_tensor(out_t, cvgs.CV_8UC3))
-    assert cvgs.kernel_name(*g_ops).startswith("pointwise4_u8_u8")  # the crop starts 9 bytes into a row: no 16-byte loads
-    cvgs.executeOperations(torch.cuda.current_stream(), *g_ops)
-    torch.cuda.synchronize()
-    oracle.execute(cvgs.lower(chain(cvgs.GpuMat.from_array(frame, cvgs.CV_8UC3), cvgs.GpuMat.from_array(ref, cvgs.CV_8UC3))))
-    H.assert_bit_exact(out_t.cpu().numpy(), ref, "unaligned crop")
+# (the unaligned crop that stays on the interpreted kernel: tests/test_gpu_colour_model.py)
 
 
 # ---- read -> convertTo -> split(std::vector<GpuMat>): the reference's tests/read/test_read_x_split.cu -------------------

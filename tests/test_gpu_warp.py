@@ -74,25 +74,7 @@ def test_warp_all_source_types_into_nchw(depth, cn, kind):
     assert ref[0][0].std() > 0
 
 
-def test_warp_many_planes_uses_device_table():
-    """More planes than travel in the kernel arguments (56): the descriptors are uploaded stream-ordered."""
-    import torch
-    src = H.random_u8((90, 120, 3), 8)
-    n = 70
-    ms = [[[1.0, 0.02 * i, 0.5 * i], [-0.01 * i, 1.0, 0.25 * i]] for i in range(n)]
-
-    def build(wrap, wrap_out, out):
-        img = wrap(src, cvgs.CV_8UC3)
-        return [cvgs.warp(cvgs.WARP_AFFINE, cvgs.CV_8UC3, [img] * n, ms, (64, 48)),
-                cvgs.split(cvgs.CV_32FC3, wrap_out(out, cvgs.CV_32FC1), (64, 48))]
-
-    gpu, ref = _both(build, (n, 3 * 64 * 48), np.float32)
-    H.assert_bit_exact(gpu[0], ref[0], "70-plane warp")
-    t = torch.zeros((90, 120, 3), dtype=torch.uint8, device="cuda:0")
-    o = torch.zeros((n, 3 * 64 * 48), dtype=torch.float32, device="cuda:0")
-    name = cvgs.kernel_name(cvgs.warp(cvgs.WARP_AFFINE, cvgs.CV_8UC3, [cvgs.GpuMat.from_tensor(t, cvgs.CV_8UC3)] * n, ms, (64, 48)),
-                            cvgs.split(cvgs.CV_32FC3, cvgs.GpuMat.from_tensor(o, cvgs.CV_32FC1), (64, 48)))
-    assert name == "warp_affine_u8c3_interp"
+# (the 70-plane warp whose descriptors are uploaded as a table runs, unchanged, as the first subtest of tests/test_gpu_warp_edges.py)
 
 
 def test_fk_cast_truncation_on_gpu():

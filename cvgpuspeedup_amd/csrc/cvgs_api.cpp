@@ -73,6 +73,12 @@ bool is_nv12(int kind) { return kind == CVGS_READ_NV12 || kind == CVGS_READ_NV12
 bool is_yuv422(int layout) { return layout == CVGS_YUV_YUYV || layout == CVGS_YUV_UYVY; } // packed 4:2:2: one plane of 4-byte pixel pairs
 bool is_yuv444(int layout) { return layout == CVGS_YUV_I444; } // planar 4:4:4: three full-resolution planes, uv_offset apart
 bool is_warp(int kind) { return kind == CVGS_READ_WARP_AFFINE || kind == CVGS_READ_WARP_PERSPECTIVE; }
+// INTER_AREA: the bilinear resize's fields, geometry and plane table, kernels of its own (k_area.hip).  NOT in is_resize(): every site that
+// asks is_resize() means "a bilinear kernel may serve this"; the sites that mean "planes carry plane_geometry" ask has_geometry().
+bool is_area(int kind) { return kind == CVGS_READ_RESIZE_AREA; }
+bool has_geometry(int kind) { return is_resize(kind) || is_area(kind); }
+// The submission paths that have no AREA kernel refuse the kind before they touch anything else (handle, stream, device).
+const char* const kAreaRefusal = ": INTER_AREA reads (CVGS_READ_RESIZE_AREA) are served by cvgs_execute / cvgs_execute_many only";
 
 // plane_geometry (host half of fk::Resize::build: the scale factors and the aspect-ratio window): cvgs_geometry.h, shared with k_boxes.hip
 
@@ -182,7 +188,7 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
         return fail(CVGS_ERR_INVALID, "unknown chain flags");
     const cvgs_read_desc& rd = ch->read;
     const cvgs_write_desc& wr = ch->write;
-    if (rd.kind < CVGS_READ_PIXEL || rd.kind > CVGS_READ_WARP_PERSPECTIVE) return fail(CVGS_ERR_INVALID, "bad read kind");
+    if (rd.kind < CVGS_READ_PIXEL || rd.kind > CVGS_READ_RESIZE_AREA) return fail(CVGS_ERR_INVALID, "bad read kind");
     if (rd.batch < 1 || rd.batch > 65535) return fail(CVGS_ERR_INVALID, "batch must be in [1, 65535]");
     if (rd.used_planes < 0 || rd.used_planes > rd.batch) return fail(CVGS_ERR_INVALID, "used_planes out of range");
     if (!rd.src) return fail(CVGS_ERR_INVALID, "read.src is null");
@@ -210,7 +216,8 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
             if (sdepth == CVGS_DEPTH_64F) return fail(CVGS_ERR_UNSUPPORTED, "device warp tables: CV_64F sources take host descriptors");
         } else if (!rd.warp_matrices) return fail(CVGS_ERR_INVALID, "read.warp_matrices is null");
     }
-    if (is_resize(rd.kind)) {
+    if (is_area(rd.kind) && sdepth == CVGS_DEPTH_64F) return fail(CVGS_ERR_UNSUPPORTED, "INTER_AREA reads of CV_64F sources (no kernel: convert the source first)");
+    if (has_geometry(rd.kind)) {
         if (rd.dst_width < 1 || rd.dst_height < 1) return fail(CVGS_ERR_INVALID, "resize target must be positive");
         if (rd.dst_width > kMaxDim || rd.dst_height > kMaxDim) return fail(CVGS_ERR_UNSUPPORTED, "resize target wider or taller than 2^24 pixels");
         if (rd.aspect_ratio < CVGS_PRESERVE_AR || rd.aspect_ratio > CVGS_PRESERVE_AR_LEFT)
@@ -235,7 +242,7 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
     R.cn = scn;
     R.batch = rd.batch;
     R.used = rd.used_planes;
-    R.is_resize = is_resize(rd.kind);
+    R.is_resize = has_geometry(rd.kind); // (AREA chains never reach a kernel that reads this as "bilinear": dispatch)
     for (int c = 0; c < 4; ++c) R.bg[c] = rd.background[c];
     R.yuv_range = rd.yuv_range;
     R.yuv_primaries = rd.yuv_primaries;
@@ -405,6 +412,8 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
         }
     }
     if (sdepth == CVGS_DEPTH_64F || L.final_depth == CVGS_DEPTH_64F) L.uses_64f = true;
+    if (is_area(rd.kind) && L.uses_64f) return fail(CVGS_ERR_UNSUPPORTED, "INTER_AREA chains with CV_64F values (no kernel: the interpreted AREA kernel computes in fp32)");
+    if (is_area(rd.kind) && wr.n_mirrors > 0) return fail(CVGS_ERR_UNSUPPORTED, "mirrors on INTER_AREA chains");
 
     // ---- write stage ----
     if (wr.kind < CVGS_WRITE_PIXEL_2D || wr.kind > CVGS_WRITE_PIXEL_2D_BATCH) return fail(CVGS_ERR_INVALID, "bad write kind");
@@ -874,7 +883,8 @@ int dispatch(const cvgs_chain_desc* ch, Lowered& L, hipStream_t stream, bool dry
     // 65 .. CVGS_KERNARG_PLANES_MAX planes of a chain K1 serves with a planar tensor target: the descriptors still travel in
     // the kernel arguments (a 16 KB block) -- no staging copy, capturable into a HIP graph
     bool big_inline = false;
-    if (!warp && !L.uses_64f && !L.int_arith && !L.args.read.table && !(ch->flags & CVGS_CHAIN_FORCE_GENERIC) &&
+    const bool area = is_area(L.args.read.kind);
+    if (!warp && !area && !L.uses_64f && !L.int_arith && !L.args.read.table && !(ch->flags & CVGS_CHAIN_FORCE_GENERIC) &&
         (int)L.planes.size() > CVGS_KERNARG_PLANES && (int)L.planes.size() <= kKernargPlanesBig)
     {
         LaunchCtx probe(stream);
@@ -934,6 +944,12 @@ int dispatch(const cvgs_chain_desc* ch, Lowered& L, hipStream_t stream, bool dry
         if (rc) return rc;
     }
     int rc = 0;
+    if (area) { // its own launcher, and nothing below: every kernel further down would read the planes as bilinear taps
+        if (has_mirrors || L.uses_64f) return fail(CVGS_ERR_UNSUPPORTED, "mirrors / CV_64F values on INTER_AREA chains");
+        if (launch_area(L.args, inline_planes, n_inline, ch->flags, stream, dry_run, info)) return fail(CVGS_ERR_HIP, "area kernel launch failed");
+        up.done(true);
+        return CVGS_OK;
+    }
     if (L.uses_64f) {
         if (has_mirrors) return fail(CVGS_ERR_UNSUPPORTED, "mirrors on CV_64F chains");
         rc = launch_generic64(L.args, L.p64, inline_planes, n_inline, stream, dry_run, info);
@@ -1374,14 +1390,14 @@ int cvgs_plane_table_build(const cvgs_read_desc* read, void* host_out) {
     ch.read = *read;
     // a throw-away write stage so that lower() can be reused for validation of the read stage
     const int out_cn = is_nv12(read->kind) ? (read->yuv_alpha ? 4 : 3) : CVGS_TYPE_CN(read->src_type);
-    const int out_depth = (is_resize(read->kind) || is_nv12(read->kind)) ? CVGS_DEPTH_32F : CVGS_TYPE_DEPTH(read->src_type);
+    const int out_depth = (has_geometry(read->kind) || is_nv12(read->kind)) ? CVGS_DEPTH_32F : CVGS_TYPE_DEPTH(read->src_type);
     ch.write.kind = CVGS_WRITE_PIXEL_3D;
     ch.write.dst_type = CVGS_MAKETYPE(out_depth, out_cn) | (out_depth == CVGS_DEPTH_16F ? (read->src_type & CVGS_TYPE_FLAG_BF16) : 0);
     ch.write.data = (void*)(uintptr_t)16;
     ch.write.planes = read->batch;
     Lowered L;
     // extent: unknown to the caller for pixel reads, so take it from the planes
-    if (is_resize(read->kind)) { ch.write.width = read->dst_width; ch.write.height = read->dst_height; }
+    if (has_geometry(read->kind)) { ch.write.width = read->dst_width; ch.write.height = read->dst_height; }
     else if (read->src && read->batch > 0) {
         ch.write.width = ((const cvgs_image2d*)read->src)[0].width;
         ch.write.height = ((const cvgs_image2d*)read->src)[0].height;
@@ -1428,6 +1444,7 @@ int cvgs_plane_tables_from_boxes(const cvgs_box_table_desc* descs, int32_t n, cv
         const cvgs_box_table_desc& d = descs[i];
         if (d.struct_size != sizeof(cvgs_box_table_desc)) return fail(CVGS_ERR_INVALID, "cvgs_box_table_desc size mismatch (ABI)");
         if (d.flags) return fail(CVGS_ERR_INVALID, "plane_tables_from_boxes: flags must be 0");
+        if (is_area(d.read_kind)) return fail(CVGS_ERR_UNSUPPORTED, "plane_tables_from_boxes: an INTER_AREA chain takes the table of the same chain spelled CVGS_READ_RESIZE_LINEAR (one layout: build it with that kind)");
         if (d.read_kind < CVGS_READ_PIXEL || d.read_kind > CVGS_READ_WARP_PERSPECTIVE) return fail(CVGS_ERR_INVALID, "bad read kind");
         if (is_warp(d.read_kind)) return fail(CVGS_ERR_UNSUPPORTED, "plane_tables_from_boxes: warp reads (WARP_AFFINE / WARP_PERSPECTIVE) take host descriptors");
         if (!is_resize(d.read_kind))
@@ -1666,6 +1683,7 @@ int cvgs_circular_create_ex(cvgs_circular_t* out, int32_t width, int32_t height,
 }
 
 int cvgs_circular_update(cvgs_circular_t ct, const cvgs_chain_desc* chain, cvgs_stream_t stream) {
+    if (chain && is_area(chain->read.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("CircularTensor::update") + kAreaRefusal);
     if (!ct || !chain) return fail(CVGS_ERR_INVALID, "null argument");
     if (!ct->capturable) {
         // the slot arithmetic of the default path lives on the host (ring index, like the reference): a captured update would
@@ -1958,6 +1976,7 @@ static int queue_submit_one(cvgs_queue_t h, const cvgs_chain_desc* chain, uint64
 }
 
 int cvgs_queue_submit(cvgs_queue_t h, const cvgs_chain_desc* chain, uint64_t* ticket) {
+    if (chain && is_area(chain->read.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kAreaRefusal);
     if (!h) return fail(CVGS_ERR_INVALID, "null queue");
     DeviceGuard guard;
     if (int rc = guard.enter(h->device)) return rc;
@@ -1965,6 +1984,8 @@ int cvgs_queue_submit(cvgs_queue_t h, const cvgs_chain_desc* chain, uint64_t* ti
 }
 
 int cvgs_queue_submit_many(cvgs_queue_t h, const cvgs_chain_desc* const* chains, int32_t n, uint64_t* last_ticket) {
+    for (int32_t i = 0; chains && i < n; ++i)
+        if (chains[i] && is_area(chains[i]->read.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kAreaRefusal);
     if (!h || !chains || n < 1) return fail(CVGS_ERR_INVALID, "null queue / no chains");
     DeviceGuard guard;
     if (int rc = guard.enter(h->device)) return rc;
@@ -1976,6 +1997,7 @@ int cvgs_queue_submit_many(cvgs_queue_t h, const cvgs_chain_desc* const* chains,
 }
 
 int cvgs_queue_submit_on(cvgs_queue_t h, const cvgs_chain_desc* chain, cvgs_stream_t stream, uint32_t flags, uint64_t* ticket) {
+    if (chain && is_area(chain->read.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kAreaRefusal);
     if (!h) return fail(CVGS_ERR_INVALID, "null queue");
     if (flags & ~(uint32_t)(CVGS_QUEUE_SUBMIT_DEFER_WAIT | CVGS_QUEUE_SUBMIT_HYBRID | CVGS_QUEUE_SUBMIT_MIN_GROUP(0xff))) return fail(CVGS_ERR_INVALID, "queue: unknown submit flag bits");
     DeviceGuard guard;
@@ -2005,6 +2027,8 @@ int cvgs_queue_submit_on(cvgs_queue_t h, const cvgs_chain_desc* chain, cvgs_stre
 }
 
 int cvgs_queue_submit_many_on(cvgs_queue_t h, const cvgs_chain_desc* const* chains, int32_t n, cvgs_stream_t stream, uint32_t flags, uint64_t* last_ticket) {
+    for (int32_t i = 0; chains && i < n; ++i)
+        if (chains[i] && is_area(chains[i]->read.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kAreaRefusal);
     if (!h || !chains || n < 1) return fail(CVGS_ERR_INVALID, "null queue / no chains");
     if (n > CVGS_QUEUE_MAX_GROUP) return fail(CVGS_ERR_INVALID, "queue: at most CVGS_QUEUE_MAX_GROUP chains behind one gate");
     if (flags & ~(uint32_t)(CVGS_QUEUE_SUBMIT_DEFER_WAIT | CVGS_QUEUE_SUBMIT_HYBRID | CVGS_QUEUE_SUBMIT_MIN_GROUP(0xff))) return fail(CVGS_ERR_INVALID, "queue: unknown submit flag bits");

@@ -255,6 +255,10 @@ static constexpr int kInlineWarp = 52; // planes whose WarpPlane travels in the 
 int launch_warp(const ChainArgs& c, const WarpPlane* planes, int n, const WarpPlane* dev_table, uint32_t chain_flags, void* stream,
                 bool dry_run, LaunchInfo* info);
 
+// INTER_AREA resize (k_area.hip): CVGS_READ_RESIZE_AREA chains, planes as for the bilinear resize (inline up to CVGS_KERNARG_PLANES,
+// else c.read.table).  The fast kernels (u8 C3/C4 -> static program -> planar fp32 / fp16 / bf16 tensor) or the interpreted one; 0 or a HIP error code
+int launch_area(const ChainArgs& c, const PlaneParams* inline_planes, int n_inline, uint32_t chain_flags, void* stream, bool dry_run, LaunchInfo* info);
+
 // warp reads in front of a CV_64F program (k_generic64.hip)
 static constexpr int kInlineWarp64 = 8;
 int launch_warp64(const ChainArgs& c, const Prog64Args& p64, const WarpPlane* planes, int n, const WarpPlane* dev_table, void* stream,

@@ -1,0 +1,299 @@
+// k_area.hip -- INTER_AREA (box filter) resize fused in front of a pointwise chain and a write stage: CVGS_READ_RESIZE_AREA.
+// An engine extension for DECIMATING crops (the reference resizes with INTER_LINEAR only): every source pixel of the view is weighted
+// by the share of it the output pixel covers, where the bilinear kernels read 2 x 2 of them.  The planes are the bilinear resize's
+// PlaneParams (fx, fy, window), inline in the kernel arguments or in a device table.
+// The arithmetic is the contract written down in include/cvgs_hip.h (strict fp32, every operation rounded once, in the written order);
+// BOTH kernels below run the same text for it (area_axis / area_w, the same loop nest), so the fast kernel is bit-identical to the
+// interpreted one.  One lane = one output pixel; the tap loops are dynamic loops over the footprint and every weight is recomputed from
+// (a, b, index) inside them: no per-lane arrays, nothing in scratch or LDS.  Adjacent lanes own adjacent footprints, so a wave's loads of
+// one source row form one contiguous span.
+#include <type_traits>
+
+#include "k_taps.hpp"
+
+namespace cvgs {
+
+// One axis of one output pixel: the taps are source indices i0 .. i0 + cnt - 1 (clamped to n - 1), tap j weighs area_w(A, j), W is their sum.
+struct AreaAxis {
+    float a, b; // shrinking: the footprint [a, b) in source pixels; not shrinking: a = the bilinear source position, b unused
+    float W;
+    int i0, cnt;
+    bool shrink;
+};
+
+__device__ __forceinline__ float area_w(const AreaAxis& A, int j) {
+    if (A.shrink) {
+        if (A.b <= A.a) return 1.0f; // (a footprint that rounding emptied: the single tap i0)
+        const int i = A.i0 + j;
+        return fminf((float)(i + 1), A.b) - fmaxf((float)i, A.a);
+    }
+    return j == 0 ? (float)(A.i0 + 1) - A.a : A.a - (float)A.i0; // the bilinear pair
+}
+
+// t = output coordinate inside the window, f = source step per output pixel, n = source extent
+__device__ __forceinline__ AreaAxis area_axis(int t, float f, int n) {
+    AreaAxis A;
+    A.shrink = f > 1.0f;
+    A.a = (float)t * f;
+    if (A.shrink) {
+        A.b = fminf((float)(t + 1) * f, (float)n);
+        A.i0 = min((int)floorf(A.a), n - 1);
+        const int i1 = max(min((int)ceilf(A.b), n), A.i0 + 1);
+        A.cnt = i1 - A.i0;
+        float W = 0.0f;
+        for (int j = 0; j < A.cnt; ++j) W = W + area_w(A, j);
+        A.W = W;
+    } else {
+        A.b = 0.0f;
+        A.i0 = (int)floorf(A.a);
+        A.cnt = 2;
+        A.W = 1.0f; // by definition, not summed
+    }
+    return A;
+}
+
+// ---- the interpreted kernel: every source type the bilinear resize reads (CV_64F excepted), interpreted program, generic write stage ----
+template <int NPL>
+__global__ __launch_bounds__(256) void k_area(const KernArgs<NPL> a) {
+    const ChainArgs& c = a.c;
+    const ReadArgs& r = c.read;
+    const int x = blockIdx.x * 64 + threadIdx.x;
+    const int y = blockIdx.y * 4 + threadIdx.y;
+    const int z = blockIdx.z;
+    if (x >= r.dst_w || y >= r.dst_h) return;
+
+    Px p;
+    p.v[0] = p.v[1] = p.v[2] = p.v[3] = 0.f;
+    int depth = CVGS_DEPTH_32F, cn = r.out_cn;
+    if (z >= r.used) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) p.v[k] = r.bg[k]; // fk::BatchRead default value, then the whole chain
+    } else {
+        PlaneParams P;
+        if constexpr (NPL == 0) P = r.table[z];
+        else P = a.planes[z];
+        if (x >= P.x1 && x <= P.x2 && y >= P.y1 && y <= P.y2) {
+            const AreaAxis X = area_axis(x - P.x1, P.fx, P.w), Y = area_axis(y - P.y1, P.fy, P.h);
+            float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            for (int jj = 0; jj < Y.cnt; ++jj) {
+                const float wy = area_w(Y, jj);
+                const int j = max(min(Y.i0 + jj, P.h - 1), 0);
+                const uint8_t* const rp = P.data + (size_t)j * (size_t)P.step;
+                float row[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                for (int ii = 0; ii < X.cnt; ++ii) {
+                    const float wx = area_w(X, ii);
+                    const int i = max(min(X.i0 + ii, P.w - 1), 0);
+                    Px t;
+                    load_px(rp, r.depth, r.cn, i, t);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (k < r.cn) row[k] = row[k] + tap_f(t.v[k], r.depth) * wx;
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[k] = acc[k] + row[k] * wy;
+            }
+            const float inv = 1.0f / (X.W * Y.W);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) p.v[k] = acc[k] * inv;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) p.v[k] = r.bg[k];
+        }
+    }
+    InterpProgInt::run(c.prog, p, depth, cn);
+    const DstPlane* dst = c.write.table ? c.write.table : c.dst_inline;
+    write_px<true>(c.write, dst, x, y, z, p, depth, cn);
+}
+
+template <int NPL>
+static hipError_t launch_area_t(const ChainArgs& c, const PlaneParams* planes, int n, hipStream_t s) {
+    KernArgs<NPL> a;
+    a.c = c;
+    for (int i = 0; i < (NPL > 0 ? NPL : 1); ++i) a.planes[i] = (NPL > 0 && i < n) ? planes[i] : PlaneParams{};
+    const dim3 block(64, 4, 1);
+    const dim3 grid((c.read.dst_w + 63) / 64, (c.read.dst_h + 3) / 4, c.read.batch);
+    hipLaunchKernelGGL(k_area<NPL>, grid, block, 0, s, a);
+    return hipGetLastError();
+}
+
+// ---- fast path: u8 C3/C4 crops -> program -> planar fp32 / fp16 / bf16 tensor (the headline decimation: N person crops -> N x C x H x W) ----
+// lane = output column, wave = one output row, blockIdx.y = plane; one 4-byte load per tap, the x-axis running sums in registers per
+// channel, compile-time pointwise program, non-temporal planar rows.  Not staged through LDS (to be measured).
+struct AreaGeom {
+    uint32_t col_tiles;
+    int32_t dst_w, dst_h, used, out_w, pad;
+    int64_t img_stride, ch_stride;
+    void* out; // float* / _Float16* / __bf16* (OT)
+};
+
+typedef uint32_t area_u32u __attribute__((aligned(1)));
+typedef const __attribute__((address_space(1))) area_u32u* gptr_area_u32;
+
+// the CN bytes of pixel `col` in the low bytes of the result; never reads outside [row, row + row_bytes)
+template <int CN>
+__device__ __forceinline__ uint32_t area_tap_u8(gptr_u8 row, int col, int row_bytes) {
+    const int o = col * CN;
+    if constexpr (CN == 4) {
+        return *(gptr_area_u32)(row + o);
+    } else {
+        if (row_bytes >= 4) { // uniform per plane; o <= row_bytes - 3: the row's last pixel is read one byte further left and shifted
+            const int ol = min(o, row_bytes - 4);
+            return *(gptr_area_u32)(row + ol) >> ((o - ol) * 8);
+        }
+        return (uint32_t)row[0] | ((uint32_t)row[1] << 8) | ((uint32_t)row[2] << 16); // a one-pixel row
+    }
+}
+
+template <int CN, int NPL, class Prog, typename OT>
+__global__ __launch_bounds__(256) void k_area_fast(const KernArgs<NPL> a, const AreaGeom g) {
+    const ChainArgs& c = a.c;
+    const int z = (int)blockIdx.y;
+    const int dst_w = g.dst_w, dst_h = g.dst_h, used = g.used, W = g.out_w;
+    int col_tile = 0, row_tile = (int)blockIdx.x;
+    if (g.col_tiles > 1) {
+        col_tile = (int)(blockIdx.x % g.col_tiles);
+        row_tile = (int)(blockIdx.x / g.col_tiles);
+    }
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = (int)(threadIdx.x & 63);
+    const int x = col_tile * 64 + lane;
+    const int y = row_tile * 4 + wave;
+    if (y >= dst_h || x >= dst_w) return;
+
+    Px p;
+    p.v[0] = p.v[1] = p.v[2] = p.v[3] = 0.f;
+    if (z >= used) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) p.v[k] = c.read.bg[k];
+    } else {
+        PlaneParams P;
+        if constexpr (NPL == 0) P = c.read.table[z];
+        else P = a.planes[z];
+        if (x >= P.x1 && x <= P.x2 && y >= P.y1 && y <= P.y2) {
+            const AreaAxis X = area_axis(x - P.x1, P.fx, P.w), Y = area_axis(y - P.y1, P.fy, P.h);
+            const int row_bytes = P.w * CN;
+            float acc[CN];
+#pragma unroll
+            for (int k = 0; k < CN; ++k) acc[k] = 0.0f;
+            for (int jj = 0; jj < Y.cnt; ++jj) {
+                const float wy = area_w(Y, jj);
+                const int j = max(min(Y.i0 + jj, P.h - 1), 0);
+                const gptr_u8 rp = (gptr_u8)P.data + (size_t)j * (size_t)P.step;
+                float row[CN];
+#pragma unroll
+                for (int k = 0; k < CN; ++k) row[k] = 0.0f;
+                for (int ii = 0; ii < X.cnt; ++ii) {
+                    const float wx = area_w(X, ii);
+                    const int i = max(min(X.i0 + ii, P.w - 1), 0);
+                    const uint32_t v = area_tap_u8<CN>(rp, i, row_bytes);
+#pragma unroll
+                    for (int k = 0; k < CN; ++k) row[k] = row[k] + (float)((v >> (8 * k)) & 0xffu) * wx;
+                }
+#pragma unroll
+                for (int k = 0; k < CN; ++k) acc[k] = acc[k] + row[k] * wy;
+            }
+            const float inv = 1.0f / (X.W * Y.W);
+#pragma unroll
+            for (int k = 0; k < CN; ++k) p.v[k] = acc[k] * inv;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) p.v[k] = c.read.bg[k];
+        }
+    }
+    int depth = CVGS_DEPTH_32F, cn = CN;
+    Prog::run(c.prog, p, depth, cn);
+    OT* const orow = (OT*)g.out + (int64_t)z * g.img_stride + (int64_t)y * W;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (k < cn) st_nt(orow + (int64_t)k * g.ch_stride + x, p.v[k]); // OT = _Float16 / __bf16: the chain's trailing CAST
+}
+
+template <int CN, class Prog, typename OT>
+static hipError_t launch_area_fast_t(const ChainArgs& c, const PlaneParams* planes, int n, hipStream_t s) {
+    AreaGeom g;
+    g.col_tiles = (uint32_t)((c.read.dst_w + 63) / 64);
+    g.dst_w = c.read.dst_w; g.dst_h = c.read.dst_h; g.used = c.read.used; g.out_w = c.write.width; g.pad = 0;
+    g.img_stride = c.write.img_stride; g.ch_stride = c.write.ch_stride;
+    g.out = c.write.data;
+    const dim3 grid(g.col_tiles * (uint32_t)((c.read.dst_h + 3) / 4), (unsigned)c.read.batch);
+    if (c.read.table) {
+        KernArgs<0> a;
+        a.c = c;
+        a.planes[0] = PlaneParams{};
+        hipLaunchKernelGGL((k_area_fast<CN, 0, Prog, OT>), grid, dim3(256), 0, s, a, g);
+    } else {
+        KernArgs<CVGS_KERNARG_PLANES> a;
+        a.c = c;
+        for (int i = 0; i < CVGS_KERNARG_PLANES; ++i) a.planes[i] = i < n ? planes[i] : PlaneParams{};
+        hipLaunchKernelGGL((k_area_fast<CN, CVGS_KERNARG_PLANES, Prog, OT>), grid, dim3(256), 0, s, a, g);
+    }
+    return hipGetLastError();
+}
+
+template <int CN, typename OT>
+static hipError_t launch_area_fast_ot(int prog_id, const ChainArgs& c, const PlaneParams* planes, int n, hipStream_t s) {
+    if (prog_id == 0) return launch_area_fast_t<CN, ProgSwapMulSubDiv, OT>(c, planes, n, s);
+    if (prog_id == 1) return launch_area_fast_t<CN, ProgMulSubDiv, OT>(c, planes, n, s);
+    return launch_area_fast_t<CN, InterpProg, OT>(c, planes, n, s);
+}
+template <int CN>
+static hipError_t launch_area_fast_cn(int ot, int prog_id, const ChainArgs& c, const PlaneParams* planes, int n, hipStream_t s) {
+    if (ot == 2) return launch_area_fast_ot<CN, __bf16>(prog_id, c, planes, n, s);
+    if (ot == 1) return launch_area_fast_ot<CN, _Float16>(prog_id, c, planes, n, s);
+    return launch_area_fast_ot<CN, float>(prog_id, c, planes, n, s);
+}
+
+// 1 = took it, 0 = not eligible
+static int try_area_fast(const ChainArgs& c_in, const PlaneParams* planes, int n, hipStream_t s, bool dry_run, LaunchInfo* info, hipError_t* err) {
+    const ReadArgs& r = c_in.read;
+    if (r.depth != CVGS_DEPTH_8U || (r.cn != 3 && r.cn != 4) || r.batch > 65535) return 0;
+    if ((c_in.write.kind != CVGS_WRITE_TENSOR_SPLIT && c_in.write.kind != CVGS_WRITE_TENSOR_T_SPLIT) || c_in.write.data2) return 0;
+    const bool bf16 = c_in.write.depth == kDepthBF16;
+    const bool f16 = c_in.write.depth == CVGS_DEPTH_16F || bf16; // a 16-bit float store
+    if (!f16 && c_in.write.depth != CVGS_DEPTH_32F) return 0;
+    ChainArgs c_cut;
+    if (f16) { // the trailing CAST moves into the store
+        if (c_in.prog.n < 1 || c_in.prog.opcode[c_in.prog.n - 1] != CVGS_OP_CAST) return 0;
+        c_cut = c_in;
+        c_cut.prog.n -= 1;
+    }
+    const ChainArgs& c = f16 ? c_cut : c_in;
+    for (int k = 0; k < c.prog.n; ++k)
+        if (c.prog.opcode[k] == CVGS_OP_CAST || c.prog.opcode[k] == CVGS_OP_CAST_TRUNC) return 0;
+    const ProgArgs& p = c.prog;
+    const int swap = r.cn == 3 ? (2 | (1 << 2) | (0 << 4)) : (2 | (1 << 2) | (0 << 4) | (3 << 6));
+    int prog_id = 2;
+    if (p.n == 4 && p.opcode[0] == CVGS_OP_REORDER && p.aux[0] == swap && p.opcode[1] == CVGS_OP_MUL && p.opcode[2] == CVGS_OP_SUB &&
+        p.opcode[3] == CVGS_OP_DIV)
+        prog_id = 0;
+    else if (p.n == 3 && p.opcode[0] == CVGS_OP_MUL && p.opcode[1] == CVGS_OP_SUB && p.opcode[2] == CVGS_OP_DIV)
+        prog_id = 1;
+    if (info) {
+        static const char* names[2][3] = {{"area_u8c3_swap_mul_sub_div", "area_u8c3_mul_sub_div", "area_u8c3_interp"},
+                                          {"area_u8c4_swap_mul_sub_div", "area_u8c4_mul_sub_div", "area_u8c4_interp"}};
+        static const char* names16[2][3] = {{"area_u8c3_swap_mul_sub_div_f16", "area_u8c3_mul_sub_div_f16", "area_u8c3_interp_f16"},
+                                            {"area_u8c4_swap_mul_sub_div_f16", "area_u8c4_mul_sub_div_f16", "area_u8c4_interp_f16"}};
+        info->kernel = f16 ? names16[r.cn == 4][prog_id] : names[r.cn == 4][prog_id];
+        if (bf16) info->kernel = bf16_kernel_name(info->kernel);
+    }
+    if (dry_run) return 1;
+    const int ot = bf16 ? 2 : (f16 ? 1 : 0);
+    *err = r.cn == 3 ? launch_area_fast_cn<3>(ot, prog_id, c, planes, n, s) : launch_area_fast_cn<4>(ot, prog_id, c, planes, n, s);
+    return 1;
+}
+
+int launch_area(const ChainArgs& c, const PlaneParams* inline_planes, int n_inline, uint32_t chain_flags, void* stream, bool dry_run, LaunchInfo* info) {
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipSuccess;
+    if (!c.read.table && n_inline > CVGS_KERNARG_PLANES) return -1; // (the caller stages larger batches into a table)
+    if (!(chain_flags & CVGS_CHAIN_FORCE_GENERIC) && try_area_fast(c, inline_planes, n_inline, s, dry_run, info, &e))
+        return e == hipSuccess ? 0 : -(int)e - 1000;
+    if (info) info->kernel = "area_interp";
+    if (dry_run) return 0;
+    if (c.read.table) e = launch_area_t<0>(c, nullptr, 0, s);
+    else if (n_inline <= 8) e = launch_area_t<8>(c, inline_planes, n_inline, s);
+    else e = launch_area_t<CVGS_KERNARG_PLANES>(c, inline_planes, n_inline, s);
+    return e == hipSuccess ? 0 : -(int)e - 1000;
+}
+
+} // namespace cvgs

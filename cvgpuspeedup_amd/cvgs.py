@@ -26,6 +26,7 @@ for _c in (1, 2, 3, 4):
     globals()["CV_16BFC%d" % _c] = make_type(DEPTH_16F, _c) | capi.TYPE_FLAG_BF16
 
 INTER_LINEAR = 1
+INTER_AREA = 3  # cv::INTER_AREA: the box filter for decimating crops (an engine extension: capi.READ_RESIZE_AREA)
 COLOR_BGR2BGRA = COLOR_RGB2RGBA = 0
 COLOR_BGRA2BGR = COLOR_RGBA2RGB = 1
 COLOR_BGR2RGBA = COLOR_RGB2BGRA = 2
@@ -38,7 +39,8 @@ COLOR_BGRA2GRAY = 10
 COLOR_RGBA2GRAY = 11
 # reference include/cv2cuda_types.cuh:77-86
 SUPPORTED_COLOR_CONVERSIONS = (0, 1, 2, 3, 4, 5, 6, 7, 10, 11)
-SUPPORTED_INTERPOLATIONS = (INTER_LINEAR,)
+SUPPORTED_INTERPOLATIONS = (INTER_LINEAR, INTER_AREA)
+_RESIZE_KIND = {INTER_LINEAR: capi.READ_RESIZE_LINEAR, INTER_AREA: capi.READ_RESIZE_AREA}
 
 PRESERVE_AR, IGNORE_AR, PRESERVE_AR_RN_EVEN, PRESERVE_AR_LEFT = 0, 1, 2, 3  # cvGS::AspectRatio
 NewestFirst, OldestFirst = capi.NEWEST_FIRST, capi.OLDEST_FIRST                # fk::CircularTensorOrder
@@ -169,7 +171,7 @@ class ReadIOp:
     def out_type(self):
         if self.kind == capi.READ_PIXEL:
             return self.src_type
-        if self.kind in (capi.READ_RESIZE_LINEAR, capi.READ_WARP_AFFINE, capi.READ_WARP_PERSPECTIVE):
+        if self.kind in (capi.READ_RESIZE_LINEAR, capi.READ_RESIZE_AREA, capi.READ_WARP_AFFINE, capi.READ_WARP_PERSPECTIVE):
             return make_type(DEPTH_32F, type_cn(self.src_type))  # reference :227: CV_32F of same channels
         return make_type(DEPTH_32F, 4 if self.yuv[2] else 3)
 
@@ -205,7 +207,7 @@ def resize(src_type, interp, mats, dsize, used_planes=None, background=None, ar=
     if single and (w == 0 or h == 0):  # dsize from fx, fy like cv::resize
         w = int(round(mats[0].cols * fx))
         h = int(round(mats[0].rows * fy))
-    return ReadIOp(capi.READ_RESIZE_LINEAR, src_type, mats, used_planes, (w, h), ar, background)
+    return ReadIOp(_RESIZE_KIND[interp], src_type, mats, used_planes, (w, h), ar, background)
 
 
 WARP_AFFINE, WARP_PERSPECTIVE = 0, 1  # fk::WarpType
@@ -729,11 +731,16 @@ def plane_tables_from_boxes(stream, descs):
     capi.check(lib.cvgs_plane_tables_from_boxes(arr, len(descs), stream_handle(stream)))
 
 
-def resize_boxes(frame, table, max_boxes, dsize, background=None, ar=IGNORE_AR, yuv=None, layout=capi.YUV_NV12):
+def resize_boxes(frame, table, max_boxes, dsize, background=None, ar=IGNORE_AR, yuv=None, layout=capi.YUV_NV12, interp=INTER_LINEAR):
     """The batched read "resize from a device-built table of `frame`": batch = used_planes = max_boxes (validity is per plane, inside the
     table), and the chain states the whole frame's byte range (cvgs_plane_table_hull of the one whole-frame view) for the independence
-    check of cvgs_execute_many.  yuv = (range, primaries, alpha) makes it the NV12 / NV21 read of a decoder surface."""
-    kind = capi.READ_NV12_RESIZE_LINEAR if yuv is not None else capi.READ_RESIZE_LINEAR
+    check of cvgs_execute_many.  yuv = (range, primaries, alpha) makes it the NV12 / NV21 read of a decoder surface.  interp = INTER_AREA
+    reads the SAME table (built with kind READ_RESIZE_LINEAR: one layout) through the box filter; pixel frames only."""
+    if interp not in SUPPORTED_INTERPOLATIONS:
+        raise ValueError("Interpolation type not supported yet.")
+    if interp == INTER_AREA and yuv is not None:
+        raise ValueError("INTER_AREA reads pixel frames: there is no area variant of the NV12 kinds")
+    kind = capi.READ_NV12_RESIZE_LINEAR if yuv is not None else _RESIZE_KIND[interp]
     whole = ReadIOp(kind, frame.cv_type, [frame], 1, (int(dsize[0]), int(dsize[1])), ar, background, yuv)
     whole.yuv_layout = layout if yuv is not None else 0
     rd = ReadIOp(kind, frame.cv_type, None, int(max_boxes), (int(dsize[0]), int(dsize[1])), ar, background, yuv, table=_dev_ptr(table),

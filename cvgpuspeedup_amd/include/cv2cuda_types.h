@@ -72,7 +72,7 @@ template <int CODE, int... CODES> struct one_of_c<CODE, CodesList<CODES...>> : s
 using SupportedColorConversions =
     CodesList<cv::COLOR_BGR2BGRA, cv::COLOR_BGRA2BGR, cv::COLOR_BGR2RGBA, cv::COLOR_BGRA2RGB, cv::COLOR_BGR2RGB,
               cv::COLOR_BGRA2RGBA, cv::COLOR_RGB2GRAY, cv::COLOR_RGBA2GRAY, cv::COLOR_BGR2GRAY, cv::COLOR_BGRA2GRAY>;
-using SupportedInterpolations = CodesList<cv::INTER_LINEAR>;
+using SupportedInterpolations = CodesList<cv::INTER_LINEAR, cv::INTER_AREA>; // INTER_AREA: engine extension (the reference lists INTER_LINEAR only)
 
 template <int CODE> constexpr bool isSupportedColorConversion = one_of_c<CODE, SupportedColorConversions>::value;
 template <int CODE> constexpr bool isSupportedInterpolation = one_of_c<CODE, SupportedInterpolations>::value;

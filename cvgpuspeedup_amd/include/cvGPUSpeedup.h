@@ -162,6 +162,7 @@ inline auto resize(const std::array<cv::cuda::GpuMat, NPtr>& input, const cv::Si
                    const cv::Scalar& backgroundValue_ = cvScalar_set<CV_MAKETYPE(CV_32F, CV_MAT_CN(T))>(0)) {
     static_assert(isSupportedInterpolation<INTER_F>, "Interpolation type not supported yet.");
     fk::BatchResizeRead<CUDA_T(T)> rd;
+    rd.kind = fk::resize_read_kind<(fk::InterpolationType)INTER_F>; // cv::INTER_AREA: the box filter (CVGS_READ_RESIZE_AREA)
     rd.planes.resize((size_t)NPtr, cvgs_image2d{nullptr, 0, 0, 0, 0});
     for (int i = 0; i < usedPlanes && i < NPtr; ++i) rd.planes[(size_t)i] = fk::image2d(gpuMat2RawPtr2D<CUDA_T(T)>(input[(size_t)i]));
     rd.used = usedPlanes;
@@ -636,7 +637,7 @@ private:
     AspectRatio ar_ = IGNORE_AR;
 };
 
-// resize<T, INTER_LINEAR, AR>(deviceCrops, backgroundValue): the batched read over the device-built table -- maxBoxes planes of the size and
+// resize<T, INTER_LINEAR | INTER_AREA, AR>(deviceCrops, backgroundValue): the batched read over the device-built table -- maxBoxes planes of the size and
 // aspect-ratio mode of the last update() (AR must be that mode), invalid boxes and the AR padding take backgroundValue.  fk::executeDivergentBatch
 // keeps refusing device tables (it selects planes on the host).
 template <int T, int INTER_F, AspectRatio AR_ = IGNORE_AR>
@@ -647,6 +648,7 @@ inline auto resize(const DeviceCrops& crops, const cv::Scalar& backgroundValue_ 
     if (f.type() != T) throw std::runtime_error("cvGS::resize(DeviceCrops): the frame of the last update() is not of type T");
     if (crops.aspectRatio() != AR_) throw std::runtime_error("cvGS::resize(DeviceCrops): AR differs from the mode the table was built with");
     fk::DeviceTableResizeRead<CUDA_T(T)> rd;
+    rd.kind = fk::resize_read_kind<(fk::InterpolationType)INTER_F>; // cv::INTER_AREA reads the same table (built as RESIZE_LINEAR: one layout)
     rd.table = crops.table();
     rd.batch = crops.maxBoxes();
     rd.dsize = fk::Size(crops.dsize().width, crops.dsize().height);

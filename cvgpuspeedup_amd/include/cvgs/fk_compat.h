@@ -98,7 +98,10 @@ struct Rect {
 };
 
 enum ND { _2D = 2, _3D = 3, T3D = 4 };
-enum InterpolationType { INTER_LINEAR = 1 };
+// INTER_AREA (cv::INTER_AREA = 3): the box filter for decimating crops, an engine extension (CVGS_READ_RESIZE_AREA, include/cvgs_hip.h)
+enum InterpolationType { INTER_LINEAR = 1, INTER_AREA = 3 };
+template <InterpolationType IT> constexpr bool interpolation_served = IT == INTER_LINEAR || IT == INTER_AREA;
+template <InterpolationType IT> constexpr int resize_read_kind = IT == INTER_AREA ? CVGS_READ_RESIZE_AREA : CVGS_READ_RESIZE_LINEAR;
 enum AspectRatio { PRESERVE_AR = 0, IGNORE_AR = 1, PRESERVE_AR_RN_EVEN = 2, PRESERVE_AR_LEFT = 3 };
 enum class CircularTensorOrder { NewestFirst = 0, OldestFirst = 1 };
 enum class ColorPlanes { Standard = 0, Transposed = 1 };
@@ -589,11 +592,12 @@ inline auto fuse(const Read<ReadYUV<PF>>& r, const Unary<ConvertYUVToRGB<PF, CR,
 template <typename T> struct ResizeRead {          // single image, pixel source
     RawPtr<_2D, T> src;
     Size dsize;
+    int kind = CVGS_READ_RESIZE_LINEAR; // or CVGS_READ_RESIZE_AREA (INTER_AREA)
     using OutputType = VectorType_t<float, cn<T>>;
     static constexpr Stage stage = Stage::Read;
     void lower(ChainBuilder& b) const {
         cvgs_read_desc& r = b.d.read;
-        r.kind = CVGS_READ_RESIZE_LINEAR; r.src_type = cvGS::cv_type_of<T>; r.batch = 1; r.used_planes = 1;
+        r.kind = kind; r.src_type = cvGS::cv_type_of<T>; r.batch = 1; r.used_planes = 1;
         r.dst_width = dsize.width; r.dst_height = dsize.height; r.aspect_ratio = CVGS_IGNORE_AR;
         b.src.assign(1, image2d(src));
     }
@@ -626,11 +630,12 @@ template <typename T> struct BatchResizeRead {
     Size dsize;
     int ar = CVGS_IGNORE_AR;
     float background[4] = {0, 0, 0, 0};
+    int kind = CVGS_READ_RESIZE_LINEAR; // or CVGS_READ_RESIZE_AREA (INTER_AREA)
     using OutputType = VectorType_t<float, cn<T>>;
     static constexpr Stage stage = Stage::Read;
     void lower(ChainBuilder& b) const {
         cvgs_read_desc& r = b.d.read;
-        r.kind = CVGS_READ_RESIZE_LINEAR; r.src_type = cvGS::cv_type_of<T>;
+        r.kind = kind; r.src_type = cvGS::cv_type_of<T>;
         r.batch = (int)planes.size(); r.used_planes = used;
         r.dst_width = dsize.width; r.dst_height = dsize.height; r.aspect_ratio = ar;
         for (int i = 0; i < 4; ++i) r.background[i] = background[i];
@@ -649,11 +654,12 @@ template <typename T> struct DeviceTableResizeRead {
     float background[4] = {0, 0, 0, 0};
     const void* src_lo = nullptr;
     const void* src_hi = nullptr;
+    int kind = CVGS_READ_RESIZE_LINEAR; // or CVGS_READ_RESIZE_AREA (INTER_AREA): the same table, read through the box filter
     using OutputType = VectorType_t<float, cn<T>>;
     static constexpr Stage stage = Stage::Read;
     void lower(ChainBuilder& b) const {
         cvgs_read_desc& r = b.d.read;
-        r.kind = CVGS_READ_RESIZE_LINEAR; r.src_type = cvGS::cv_type_of<T>;
+        r.kind = kind; r.src_type = cvGS::cv_type_of<T>;
         r.batch = batch; r.used_planes = batch;
         r.src = table; r.flags = CVGS_READ_FLAG_TABLE_ON_DEVICE;
         r.table_src_lo = src_lo; r.table_src_hi = src_hi;
@@ -671,8 +677,9 @@ template <typename T> struct BatchPixelRead {
     static constexpr Stage stage = Stage::Read;
     // crops.then(resize<INTER>(size)): every plane is stretched to dsize (IGNORE_AR), the K1 read
     template <InterpolationType IT> BatchResizeRead<T> then(const IncompleteResize<IT>& rs) const {
-        static_assert(IT == INTER_LINEAR, "Interpolation type not supported yet.");
+        static_assert(interpolation_served<IT>, "Interpolation type not supported yet.");
         BatchResizeRead<T> rd;
+        rd.kind = resize_read_kind<IT>;
         rd.planes = planes;
         rd.used = used;
         rd.dsize = rs.dsize;
@@ -789,12 +796,12 @@ template <typename Op> template <size_t N> inline auto Read<Op>::then(const Batc
     return rd;
 }
 template <typename Op> template <InterpolationType IT> inline auto Read<Op>::then(const IncompleteResize<IT>& rs) const {
-    static_assert(IT == INTER_LINEAR, "Interpolation type not supported yet.");
-    return ResizeRead<typename Op::OutputType>{params, rs.dsize};
+    static_assert(interpolation_served<IT>, "Interpolation type not supported yet.");
+    return ResizeRead<typename Op::OutputType>{params, rs.dsize, resize_read_kind<IT>};
 }
 
 template <InterpolationType IT, AspectRatio AR = IGNORE_AR> struct Resize {
-    static_assert(IT == INTER_LINEAR, "Interpolation type not supported yet.");
+    static_assert(interpolation_served<IT>, "Interpolation type not supported yet.");
     static IncompleteResize<IT> build(const Size& dsize) { return {dsize}; }
     template <typename T> static auto build(const RawPtr<_2D, T>& in, const Size& dsize, double fx = 0., double fy = 0.) {
         Size d = dsize;
@@ -802,10 +809,11 @@ template <InterpolationType IT, AspectRatio AR = IGNORE_AR> struct Resize {
             d.width = (int)std::nearbyint(in.dims.width * fx);
             d.height = (int)std::nearbyint(in.dims.height * fy);
         }
-        return ResizeRead<T>{in, d};
+        return ResizeRead<T>{in, d, resize_read_kind<IT>};
     }
     template <PixelFormat PF, ColorRange CR, ColorPrimitives CP, bool ALPHA, typename O, bool SW>
     static auto build(const YuvRead<PF, CR, CP, ALPHA, O, SW>& back, const Size& dsize, const float* background = nullptr) {
+        static_assert(IT == INTER_LINEAR, "INTER_AREA over a YUV read-back is not implemented: there is no area variant of the NV12 read kinds (resize the converted image, or use INTER_LINEAR)");
         ResizeYuvRead<YuvRead<PF, CR, CP, ALPHA, O, SW>> r{back, dsize};
         r.ar = (int)AR; // same numeric values as cvgs_aspect_ratio
         if (background)

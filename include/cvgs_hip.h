@@ -128,7 +128,32 @@ typedef enum cvgs_read_kind {
      * std::array<cv::Size, BATCH> overloads, :381-401): then the write stage must hold one destination image per plane
      * (CVGS_WRITE_PIXEL_2D_BATCH / CVGS_WRITE_SPLIT_2D) of exactly that plane's size; dense tensors need equal sizes.  */
     CVGS_READ_WARP_AFFINE = 4,
-    CVGS_READ_WARP_PERSPECTIVE = 5
+    CVGS_READ_WARP_PERSPECTIVE = 5,
+    /* INTER_AREA (box filter) resize: an ENGINE EXTENSION, the reference has INTER_LINEAR only.  For decimating crops: every source
+     * pixel of the view is weighted by the share of it the output pixel covers, where the bilinear kind reads 2 x 2 of them.  Uses the
+     * fields of CVGS_READ_RESIZE_LINEAR unchanged (src views or a device plane table, batch, used_planes, dst_width / dst_height,
+     * aspect_ratio, background, table_src_lo / _hi); the value is CV_32F of the source's channels.  The plane table of an AREA chain is
+     * BYTE FOR BYTE the table of the same chain spelled RESIZE_LINEAR (PlaneParams: fx, fy and the window x1..y2 of the aspect-ratio
+     * mode): cvgs_plane_table_build / _bytes accept the kind, and a device table written by cvgs_plane_tables_from_boxes with
+     * read_kind = CVGS_READ_RESIZE_LINEAR may be handed to an AREA chain.  cvgs_plane_table_hull of an AREA read is, per plane, the
+     * whole view (first byte of the top row to one past the last byte of the bottom row): every pixel of a shrunk view is read; for a
+     * non-shrinking axis it is a safe upper bound.
+     * The arithmetic (the contract: strict fp32, no contraction, every operation rounded once, in this order).  Output pixel (x, y) of
+     * plane z inside the window: tx = x - x1, ty = y - y1.  Each axis builds its tap list on its own; x is given, y is the same with
+     * fy, ty, h.
+     *   fx <= 1.0f (not shrinking): the bilinear taps.  s = (float)tx * fx, i0 = (int)floorf(s); tap 0 = (i0, (float)(i0 + 1) - s),
+     *     tap 1 = (min(i0 + 1, w - 1), s - (float)i0); Wx = 1.0f by definition, not summed.
+     *   fx > 1.0f (shrinking): a = (float)tx * fx, b = fminf((float)(tx + 1) * fx, (float)w), i0 = min((int)floorf(a), w - 1),
+     *     i1 = max(min((int)ceilf(b), w), i0 + 1) (exclusive); for i = i0 .. i1-1 ascending wx_i = fminf((float)(i + 1), b) -
+     *     fmaxf((float)i, a); if b <= a the single tap (i0, 1.0f); Wx = the fp32 sum of the wx_i, ascending, from 0.0f.
+     *   pixel, per channel k: acc = 0.0f; for rows j ascending { row = 0.0f; for columns i ascending row = row + v(j,i,k) * wx_i;
+     *     acc = acc + row * wy_j }; the result is acc * (1.0f / (Wx * Wy)).  v = the source sample as a float (exact for 8U, 8S, 16U,
+     *     16S, 16F, 16BF; 32F as it is; 32S converted).
+     * Outside the window: background; planes z >= used_planes: the default value, then the chain's program -- as for the bilinear kind.
+     * A view shrunk by exactly 2 on both axes gives the exact mean of each 2 x 2 block; a view as large as its target reproduces it.
+     * Served by cvgs_execute, and one by one by cvgs_execute_many.  CVGS_ERR_UNSUPPORTED: CV_64F sources or values, mirrors, the
+     * descriptor queue, cvgs_circular_update; there is no AREA variant of the NV12 kinds.                                          */
+    CVGS_READ_RESIZE_AREA = 6
 } cvgs_read_kind;
 
 /* same numeric values as cvGS::AspectRatio (reference include/cvGPUSpeedup.cuh:32) */

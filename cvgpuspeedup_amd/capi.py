@@ -68,6 +68,12 @@ READ_FLAG_TABLE_SOURCES_VOUCHED = 2
 # write kinds
 (WRITE_PIXEL_2D, WRITE_PIXEL_3D, WRITE_TENSOR_SPLIT, WRITE_TENSOR_T_SPLIT, WRITE_SPLIT_2D,
  WRITE_PIXEL_2D_BATCH) = range(6)
+WRITE_NV12 = 6  # an NV12 / NV21 encoder surface per plane, converted and subsampled by the chain's own launch (WriteDesc.yuv_params)
+
+
+def write_yuv_params(color_range, primaries, layout):
+    """WriteDesc.yuv_params of a WRITE_NV12 chain (CVGS_WRITE_YUV_PARAMS)."""
+    return (color_range & 15) | ((primaries & 15) << 4) | ((layout & 15) << 8)
 # chain flags
 CHAIN_DEFAULT, CHAIN_FORCE_GENERIC, CHAIN_NO_THREAD_FUSION = 0, 1, 2
 # circular tensor
@@ -96,7 +102,7 @@ class Op(C.Structure):
 class WriteDesc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("dst_type", C.c_int32), ("data", C.c_void_p), ("width", C.c_int32),
                 ("height", C.c_int32), ("step", C.c_int32), ("planes", C.c_int32), ("planes2d", C.c_void_p),
-                ("mirrors", C.POINTER(C.c_void_p)), ("n_mirrors", C.c_int32), ("reserved", C.c_int32)]
+                ("mirrors", C.POINTER(C.c_void_p)), ("n_mirrors", C.c_int32), ("yuv_params", C.c_int32)]
 
 
 class ChainDesc(C.Structure):

@@ -79,6 +79,10 @@ bool is_area(int kind) { return kind == CVGS_READ_RESIZE_AREA; }
 bool has_geometry(int kind) { return is_resize(kind) || is_area(kind); }
 // The submission paths that have no AREA kernel refuse the kind before they touch anything else (handle, stream, device).
 const char* const kAreaRefusal = ": INTER_AREA reads (CVGS_READ_RESIZE_AREA) are served by cvgs_execute / cvgs_execute_many only";
+// NV12 / NV21 encoder surfaces as the write stage (k_nv12_write.hip): a launcher of its own, in front of every other one (dispatch), and the
+// same rule for the submission paths that have no kernel for it.
+bool is_nv12_write(int kind) { return kind == CVGS_WRITE_NV12; }
+const char* const kNv12WriteRefusal = ": NV12 / NV21 surface writes (CVGS_WRITE_NV12) are served by cvgs_execute / cvgs_execute_many only";
 
 // plane_geometry (host half of fk::Resize::build: the scale factors and the aspect-ratio window): cvgs_geometry.h, shared with k_boxes.hip
 
@@ -189,6 +193,12 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
     const cvgs_read_desc& rd = ch->read;
     const cvgs_write_desc& wr = ch->write;
     if (rd.kind < CVGS_READ_PIXEL || rd.kind > CVGS_READ_RESIZE_AREA) return fail(CVGS_ERR_INVALID, "bad read kind");
+    if (is_nv12_write(wr.kind)) { // what has no kernel is said first, before any field of the chain is judged
+        if (circular) return fail(CVGS_ERR_UNSUPPORTED, std::string("CircularTensor::update") + kNv12WriteRefusal);
+        if (is_warp(rd.kind)) return fail(CVGS_ERR_UNSUPPORTED, "NV12 surface writes behind warp reads (no kernel: warp into an image, then convert it)");
+        if (is_area(rd.kind)) return fail(CVGS_ERR_UNSUPPORTED, "NV12 surface writes behind INTER_AREA reads (no kernel: CVGS_READ_RESIZE_AREA writes pixels and tensors)");
+        if (wr.n_mirrors > 0) return fail(CVGS_ERR_UNSUPPORTED, "mirrors on NV12 surface writes (mirrors exist for tensor write kinds)");
+    }
     if (rd.batch < 1 || rd.batch > 65535) return fail(CVGS_ERR_INVALID, "batch must be in [1, 65535]");
     if (rd.used_planes < 0 || rd.used_planes > rd.batch) return fail(CVGS_ERR_INVALID, "used_planes out of range");
     if (!rd.src) return fail(CVGS_ERR_INVALID, "read.src is null");
@@ -414,9 +424,10 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
     if (sdepth == CVGS_DEPTH_64F || L.final_depth == CVGS_DEPTH_64F) L.uses_64f = true;
     if (is_area(rd.kind) && L.uses_64f) return fail(CVGS_ERR_UNSUPPORTED, "INTER_AREA chains with CV_64F values (no kernel: the interpreted AREA kernel computes in fp32)");
     if (is_area(rd.kind) && wr.n_mirrors > 0) return fail(CVGS_ERR_UNSUPPORTED, "mirrors on INTER_AREA chains");
+    if (is_nv12_write(wr.kind) && L.uses_64f) return fail(CVGS_ERR_UNSUPPORTED, "NV12 surface writes of chains with CV_64F values (no kernel: the conversion is specified in fp32)");
 
     // ---- write stage ----
-    if (wr.kind < CVGS_WRITE_PIXEL_2D || wr.kind > CVGS_WRITE_PIXEL_2D_BATCH) return fail(CVGS_ERR_INVALID, "bad write kind");
+    if (wr.kind < CVGS_WRITE_PIXEL_2D || wr.kind > CVGS_WRITE_NV12) return fail(CVGS_ERR_INVALID, "bad write kind");
     if (type_depth(wr.dst_type) != L.final_depth || CVGS_TYPE_CN(wr.dst_type) != L.final_cn)
         return fail(CVGS_ERR_INVALID, "write type does not match the type produced by the last stage");
     WriteArgs& Wa = L.args.write;
@@ -427,6 +438,7 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
     Wa.height = L.out_h;
     Wa.step = wr.step;
     Wa.planes = wr.planes;
+    Wa.yuv_params = is_nv12_write(wr.kind) ? wr.yuv_params : 0; // (every other kind ignores the field)
     Wa.data = (uint8_t*)wr.data;
     Wa.table = nullptr;
     {
@@ -481,6 +493,29 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
             L.dst_planes[i].data = (uint8_t*)im.data;
             L.dst_planes[i].step = im.step;
             L.dst_planes[i].pad = 0;
+        }
+    }
+    if (is_nv12_write(wr.kind)) {
+        if (L.final_depth != CVGS_DEPTH_32F || L.final_cn != 3)
+            return fail(CVGS_ERR_INVALID, "NV12 surface writes take a CV_32FC3 value (R, G, B): convertTo CV_32F / drop the alpha channel first");
+        const int p = wr.yuv_params;
+        if ((p & ~0xfff) || CVGS_WRITE_YUV_RANGE(p) > CVGS_YUV_LIMITED || CVGS_WRITE_YUV_PRIMARIES(p) > CVGS_BT2020)
+            return fail(CVGS_ERR_INVALID, "NV12 surface write: bad yuv_params (range | primaries << 4 | layout << 8)");
+        if (CVGS_WRITE_YUV_LAYOUT(p) != CVGS_YUV_NV12 && CVGS_WRITE_YUV_LAYOUT(p) != CVGS_YUV_NV21)
+            return fail(CVGS_ERR_INVALID, "NV12 surface write: the layout is CVGS_YUV_NV12 or CVGS_YUV_NV21");
+        if ((L.out_w & 1) || (L.out_h & 1)) return fail(CVGS_ERR_INVALID, "NV12 planes need even dimensions");
+        if (!wr.planes2d) return fail(CVGS_ERR_INVALID, "write.planes2d is null");
+        if (!L.dst_planes.resize((size_t)rd.batch)) return fail(CVGS_ERR_HIP, "out of host memory");
+        for (size_t i = 0; i < L.dst_planes.size(); ++i) {
+            const cvgs_image2d& im = wr.planes2d[i];
+            if (!im.data || im.width != L.out_w || im.height != L.out_h || im.step < im.width)
+                return fail(CVGS_ERR_INVALID, "destination surface missing or of the wrong size");
+            if (im.uv_offset < 0) return fail(CVGS_ERR_INVALID, "NV12 uv_offset must be non-negative");
+            const int64_t uv_off = im.uv_offset ? (int64_t)im.uv_offset : (int64_t)im.height * im.step;
+            if (uv_off > INT32_MAX) return fail(CVGS_ERR_UNSUPPORTED, "4:2:0 surfaces whose luma plane exceeds 2 GiB");
+            L.dst_planes[i].data = (uint8_t*)im.data;
+            L.dst_planes[i].step = im.step;
+            L.dst_planes[i].pad = (int32_t)uv_off; // DstPlane::pad of an NV12 target: the chroma offset, resolved
         }
     }
     return CVGS_OK;
@@ -884,7 +919,8 @@ int dispatch(const cvgs_chain_desc* ch, Lowered& L, hipStream_t stream, bool dry
     // the kernel arguments (a 16 KB block) -- no staging copy, capturable into a HIP graph
     bool big_inline = false;
     const bool area = is_area(L.args.read.kind);
-    if (!warp && !area && !L.uses_64f && !L.int_arith && !L.args.read.table && !(ch->flags & CVGS_CHAIN_FORCE_GENERIC) &&
+    const bool nv12w = is_nv12_write(L.args.write.kind);
+    if (!warp && !area && !nv12w && !L.uses_64f && !L.int_arith && !L.args.read.table && !(ch->flags & CVGS_CHAIN_FORCE_GENERIC) &&
         (int)L.planes.size() > CVGS_KERNARG_PLANES && (int)L.planes.size() <= kKernargPlanesBig)
     {
         LaunchCtx probe(stream);
@@ -944,6 +980,12 @@ int dispatch(const cvgs_chain_desc* ch, Lowered& L, hipStream_t stream, bool dry
         if (rc) return rc;
     }
     int rc = 0;
+    if (nv12w) { // its own launcher, in front of every other: no existing kernel ever sees the write kind
+        if (warp || area || has_mirrors || L.uses_64f) return fail(CVGS_ERR_UNSUPPORTED, "warp / INTER_AREA reads, mirrors or CV_64F values in front of an NV12 surface write");
+        if (launch_nv12_write(L.args, inline_planes, n_inline, ch->flags, stream, dry_run, info)) return fail(CVGS_ERR_HIP, "NV12 write kernel launch failed");
+        up.done(true);
+        return CVGS_OK;
+    }
     if (area) { // its own launcher, and nothing below: every kernel further down would read the planes as bilinear taps
         if (has_mirrors || L.uses_64f) return fail(CVGS_ERR_UNSUPPORTED, "mirrors / CV_64F values on INTER_AREA chains");
         if (launch_area(L.args, inline_planes, n_inline, ch->flags, stream, dry_run, info)) return fail(CVGS_ERR_HIP, "area kernel launch failed");
@@ -1684,6 +1726,7 @@ int cvgs_circular_create_ex(cvgs_circular_t* out, int32_t width, int32_t height,
 
 int cvgs_circular_update(cvgs_circular_t ct, const cvgs_chain_desc* chain, cvgs_stream_t stream) {
     if (chain && is_area(chain->read.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("CircularTensor::update") + kAreaRefusal);
+    if (chain && is_nv12_write(chain->write.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("CircularTensor::update") + kNv12WriteRefusal);
     if (!ct || !chain) return fail(CVGS_ERR_INVALID, "null argument");
     if (!ct->capturable) {
         // the slot arithmetic of the default path lives on the host (ring index, like the reference): a captured update would
@@ -1977,6 +2020,7 @@ static int queue_submit_one(cvgs_queue_t h, const cvgs_chain_desc* chain, uint64
 
 int cvgs_queue_submit(cvgs_queue_t h, const cvgs_chain_desc* chain, uint64_t* ticket) {
     if (chain && is_area(chain->read.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kAreaRefusal);
+    if (chain && is_nv12_write(chain->write.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kNv12WriteRefusal);
     if (!h) return fail(CVGS_ERR_INVALID, "null queue");
     DeviceGuard guard;
     if (int rc = guard.enter(h->device)) return rc;
@@ -1984,8 +2028,10 @@ int cvgs_queue_submit(cvgs_queue_t h, const cvgs_chain_desc* chain, uint64_t* ti
 }
 
 int cvgs_queue_submit_many(cvgs_queue_t h, const cvgs_chain_desc* const* chains, int32_t n, uint64_t* last_ticket) {
-    for (int32_t i = 0; chains && i < n; ++i)
+    for (int32_t i = 0; chains && i < n; ++i) {
         if (chains[i] && is_area(chains[i]->read.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kAreaRefusal);
+        if (chains[i] && is_nv12_write(chains[i]->write.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kNv12WriteRefusal);
+    }
     if (!h || !chains || n < 1) return fail(CVGS_ERR_INVALID, "null queue / no chains");
     DeviceGuard guard;
     if (int rc = guard.enter(h->device)) return rc;
@@ -1998,6 +2044,7 @@ int cvgs_queue_submit_many(cvgs_queue_t h, const cvgs_chain_desc* const* chains,
 
 int cvgs_queue_submit_on(cvgs_queue_t h, const cvgs_chain_desc* chain, cvgs_stream_t stream, uint32_t flags, uint64_t* ticket) {
     if (chain && is_area(chain->read.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kAreaRefusal);
+    if (chain && is_nv12_write(chain->write.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kNv12WriteRefusal);
     if (!h) return fail(CVGS_ERR_INVALID, "null queue");
     if (flags & ~(uint32_t)(CVGS_QUEUE_SUBMIT_DEFER_WAIT | CVGS_QUEUE_SUBMIT_HYBRID | CVGS_QUEUE_SUBMIT_MIN_GROUP(0xff))) return fail(CVGS_ERR_INVALID, "queue: unknown submit flag bits");
     DeviceGuard guard;
@@ -2027,8 +2074,10 @@ int cvgs_queue_submit_on(cvgs_queue_t h, const cvgs_chain_desc* chain, cvgs_stre
 }
 
 int cvgs_queue_submit_many_on(cvgs_queue_t h, const cvgs_chain_desc* const* chains, int32_t n, cvgs_stream_t stream, uint32_t flags, uint64_t* last_ticket) {
-    for (int32_t i = 0; chains && i < n; ++i)
+    for (int32_t i = 0; chains && i < n; ++i) {
         if (chains[i] && is_area(chains[i]->read.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kAreaRefusal);
+        if (chains[i] && is_nv12_write(chains[i]->write.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kNv12WriteRefusal);
+    }
     if (!h || !chains || n < 1) return fail(CVGS_ERR_INVALID, "null queue / no chains");
     if (n > CVGS_QUEUE_MAX_GROUP) return fail(CVGS_ERR_INVALID, "queue: at most CVGS_QUEUE_MAX_GROUP chains behind one gate");
     if (flags & ~(uint32_t)(CVGS_QUEUE_SUBMIT_DEFER_WAIT | CVGS_QUEUE_SUBMIT_HYBRID | CVGS_QUEUE_SUBMIT_MIN_GROUP(0xff))) return fail(CVGS_ERR_INVALID, "queue: unknown submit flag bits");

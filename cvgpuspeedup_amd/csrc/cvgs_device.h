@@ -36,10 +36,10 @@ static_assert(sizeof(PlaneParams) == 48, "PlaneParams layout");
 
 // Device plane table = PlaneParams[batch]  (cvgs_plane_table_build).
 
-struct DstPlane {           // SPLIT_2D / PIXEL_2D_BATCH targets, 16 bytes
+struct DstPlane {           // SPLIT_2D / PIXEL_2D_BATCH / NV12 targets, 16 bytes
     uint8_t* data;
     int32_t step;
-    int32_t pad;
+    int32_t pad;            // NV12 targets: bytes from `data` to the chroma row of luma row 0 (resolved: never 0); 0 otherwise
 };
 
 struct ReadArgs {
@@ -74,7 +74,7 @@ struct WriteArgs {
     int32_t width, height;  // plane extent
     int32_t step;           // PIXEL_2D pitch (bytes)
     int32_t planes;         // tensor N (TensorTSplit stride)
-    int32_t pad;
+    int32_t yuv_params;     // CVGS_WRITE_NV12: range | primaries << 4 | layout << 8 (cvgs_write_desc.yuv_params); 0 otherwise
     uint8_t* data;
     const DstPlane* table;  // device table for SPLIT_2D / PIXEL_2D_BATCH beyond the inline ones
     // Tensor kinds: element strides of the primary target, and an optional SECOND target that receives the same
@@ -258,6 +258,11 @@ int launch_warp(const ChainArgs& c, const WarpPlane* planes, int n, const WarpPl
 // INTER_AREA resize (k_area.hip): CVGS_READ_RESIZE_AREA chains, planes as for the bilinear resize (inline up to CVGS_KERNARG_PLANES,
 // else c.read.table).  The fast kernels (u8 C3/C4 -> static program -> planar fp32 / fp16 / bf16 tensor) or the interpreted one; 0 or a HIP error code
 int launch_area(const ChainArgs& c, const PlaneParams* inline_planes, int n_inline, uint32_t chain_flags, void* stream, bool dry_run, LaunchInfo* info);
+
+// NV12 / NV21 encoder surfaces (k_nv12_write.hip): CVGS_WRITE_NV12 chains behind a per-pixel, bilinear or NV12 read, planes as for the
+// bilinear resize, targets in c.dst_inline / c.write.table (DstPlane::pad = the chroma offset).  The fast kernel (NV12 / NV21 surface ->
+// resize -> surface, empty program) or the interpreted one; 0 or a HIP error code
+int launch_nv12_write(const ChainArgs& c, const PlaneParams* inline_planes, int n_inline, uint32_t chain_flags, void* stream, bool dry_run, LaunchInfo* info);
 
 // warp reads in front of a CV_64F program (k_generic64.hip)
 static constexpr int kInlineWarp64 = 8;

@@ -435,6 +435,26 @@ def write_batch(out_type, outputs):
                     keep=outs)
 
 
+def write_nv12(mats, color_range=capi.YUV_FULL, primaries=capi.BT709, layout=capi.YUV_NV12):
+    """An NV12 / NV21 encoder surface per plane as the chain's write stage (capi.WRITE_NV12; an engine extension): the CV_32FC3 value
+    (R, G, B -- a BGR chain puts cvtColor(COLOR_BGR2RGB) in front) is converted with `color_range` / `primaries`, the chroma of every
+    2 x 2 block is averaged and the 8-bit surface is stored by the same launch.  `mats` is one GpuMat or a list: each the CV_8UC1 luma view
+    of a surface (rows = luma height) with its uv_offset, as read_nv12 takes them (0 / unset: the chroma plane directly below the luma
+    plane; GpuMat.nv12_roi gives the view of a region of a larger surface)."""
+    outs = [mats] if isinstance(mats, GpuMat) else list(mats)
+    if layout not in (capi.YUV_NV12, capi.YUV_NV21):
+        raise ValueError("write_nv12 writes layout YUV_NV12 or YUV_NV21")
+    for m in outs:
+        if m.cv_type != make_type(DEPTH_8U, 1):
+            raise ValueError("an NV12 target is the CV_8UC1 luma view of the surface")
+        if (m.cols | m.rows) & 1:
+            raise ValueError("NV12 surfaces need even width and height")
+    arr = (capi.Image2D * len(outs))(*[m.image2d() for m in outs])
+    wr = WriteIOp(capi.WRITE_NV12, make_type(DEPTH_32F, 3), 0, outs[0].cols, outs[0].rows, 0, len(outs), planes2d=arr, keep=outs)
+    wr.yuv_params = capi.write_yuv_params(color_range, primaries, layout)
+    return wr
+
+
 # ---- lowering ---------------------------------------------------------------------------------------------
 class LoweredChain:
     """A cvgs_chain_desc plus everything that must stay alive while it is in use."""
@@ -514,6 +534,7 @@ def lower(iops, flags=0):
     w.width, w.height, w.step, w.planes = wr.width, wr.height, wr.step, wr.planes
     if wr.planes2d is not None:
         w.planes2d = C.cast(wr.planes2d, C.c_void_p).value
+    w.yuv_params = getattr(wr, "yuv_params", 0)
     if getattr(wr, "mirrors", None):
         arr = (C.c_void_p * len(wr.mirrors))(*wr.mirrors)
         keep.append(arr)

@@ -142,6 +142,41 @@ inline auto write(const fk::Tensor<T>& output) {
     return fk::Write<fk::PerThreadWrite<fk::_3D, T>>{output.ptr()};
 }
 
+// writeNV12<range, primaries>(surface) / writeNV21<...>: the chain ENDS in an 8-bit 4:2:0 encoder surface (NEW: CVGS_WRITE_NV12, an engine
+// extension) -- the float3 R, G, B value is converted to Y'CbCr, the chroma of every 2 x 2 block averaged, and the surface stored by the
+// same kernel that read and resized the picture.  `surface` is a CV_8UC1 GpuMat of H * 3 / 2 rows (H luma rows, then H / 2 interleaved
+// chroma rows), as cvtColorNV12 takes it; the std::array overload writes one surface per batch element.  A BGR chain puts
+// cvtColor<cv::COLOR_BGR2RGB, CV_32FC3>() in front.
+namespace internal {
+template <size_t N>
+inline fk::Nv12SurfaceWrite nv12_surface_write(const std::array<cv::cuda::GpuMat, N>& surfaces, int range, int primaries, int layout, const char* what) {
+    fk::Nv12SurfaceWrite w;
+    w.params = CVGS_WRITE_YUV_PARAMS(range, primaries, layout);
+    for (const auto& s : surfaces) {
+        if (s.type() != CV_8UC1 || s.rows % 3 != 0 || ((s.rows / 3 * 2) & 1) || (s.cols & 1))
+            throw std::runtime_error(std::string(what) + " needs CV_8UC1 surfaces with rows = H * 3 / 2, H and the width even");
+        w.planes.push_back(cvgs_image2d{s.data, s.cols, s.rows / 3 * 2, (int32_t)s.step, 0});
+    }
+    return w;
+}
+} // namespace internal
+template <fk::ColorRange CR = fk::Full, fk::ColorPrimitives CP = fk::bt709, size_t N>
+inline auto writeNV12(const std::array<cv::cuda::GpuMat, N>& surfaces) {
+    return internal::nv12_surface_write(surfaces, (int)CR, (int)CP, CVGS_YUV_NV12, "writeNV12");
+}
+template <fk::ColorRange CR = fk::Full, fk::ColorPrimitives CP = fk::bt709>
+inline auto writeNV12(const cv::cuda::GpuMat& surface) {
+    return writeNV12<CR, CP>(std::array<cv::cuda::GpuMat, 1>{surface});
+}
+template <fk::ColorRange CR = fk::Full, fk::ColorPrimitives CP = fk::bt709, size_t N>
+inline auto writeNV21(const std::array<cv::cuda::GpuMat, N>& surfaces) {
+    return internal::nv12_surface_write(surfaces, (int)CR, (int)CP, CVGS_YUV_NV21, "writeNV21");
+}
+template <fk::ColorRange CR = fk::Full, fk::ColorPrimitives CP = fk::bt709>
+inline auto writeNV21(const cv::cuda::GpuMat& surface) {
+    return writeNV21<CR, CP>(std::array<cv::cuda::GpuMat, 1>{surface});
+}
+
 // ---- read builders ---------------------------------------------------------------------------------------------
 // resize<INTER>(dsize): a resize still waiting for its source -- complete it with readIOp.then(...)
 template <int INTER_F>

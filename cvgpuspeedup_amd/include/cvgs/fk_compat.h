@@ -395,6 +395,22 @@ template <typename T> struct BatchPixelWrite {
     }
 };
 
+// An NV12 / NV21 encoder surface per batch element (CVGS_WRITE_NV12; an engine extension, built by cvGS::writeNV12 / writeNV21): the
+// float3 R, G, B value is converted, chroma-subsampled and stored by the chain's own kernel.  `params` = CVGS_WRITE_YUV_PARAMS.
+struct Nv12SurfaceWrite {
+    detail::SmallVec<cvgs_image2d, detail::kInlinePlanes> planes; // luma views (uv_offset 0: the chroma plane directly below)
+    int32_t params = 0;
+    using InputType = float3;
+    static constexpr Stage stage = Stage::Write;
+    void lower(ChainBuilder& b) const {
+        cvgs_write_desc& w = b.d.write;
+        w.kind = CVGS_WRITE_NV12; w.dst_type = CVGS_MAKETYPE(CVGS_DEPTH_32F, 3); w.yuv_params = params;
+        b.dst.assign(planes.begin(), planes.end());
+        if (!planes.empty()) { w.width = planes[0].width; w.height = planes[0].height; }
+        w.planes = (int)planes.size();
+    }
+};
+
 template <ND D, typename T> struct PerThreadWrite;
 template <typename T> struct PerThreadWrite<_2D, T> {
     using ParamsType = RawPtr<_2D, T>;
@@ -858,6 +874,8 @@ template <typename... IOps> inline void lowerChain(ChainBuilder& b, const IOps&.
     static_assert(std::tuple_element_t<N - 1, Tuple>::stage == Stage::Write, "the last operation must be a Write");
     static_assert(detail::middle_pointwise<Tuple>(std::make_index_sequence<N - 2>{}),
                   "only Unary/Binary operations may sit between the read and the write");
+    static_assert(!std::is_same_v<std::tuple_element_t<N - 1, Tuple>, Nv12SurfaceWrite> || std::is_same_v<typename std::tuple_element_t<N - 2, Tuple>::OutputType, float3>,
+                  "writeNV12 / writeNV21 take a float3 value (CV_32FC3 in the order R, G, B): put convertTo<..., CV_32FC3> / a cvtColor that drops the alpha channel in front");
     static_assert(detail::types_chain<Tuple>(std::make_index_sequence<N - 1>{}),
                   "the output type of each operation must be the input type of the next one");
     using First = std::tuple_element_t<0, Tuple>;

@@ -298,8 +298,44 @@ typedef enum cvgs_write_kind {
      * (cvGS::split(vector<GpuMat>) / (array<vector<GpuMat>,N>) :163-183)                       */
     CVGS_WRITE_SPLIT_2D = 4,
     /* fk::PerThreadWrite<_2D,T> per batch element: array of pitched images                     */
-    CVGS_WRITE_PIXEL_2D_BATCH = 5
+    CVGS_WRITE_PIXEL_2D_BATCH = 5,
+    /* An 8-bit 4:2:0 ENCODER surface per plane, NV12 or NV21: an ENGINE EXTENSION, the reference writes pixels and tensors only.  The
+     * chain converts to Y'CbCr, subsamples the chroma and stores the surface in the same launch that read and resized the picture: what a
+     * pipeline that ends in a video encoder otherwise does in a second pass over a packed CV_8UC3 image.
+     * Value.  The value reaching the write must be CV_32FC3 (dst_type), channels in the order R, G, B; a chain that carries BGR puts a
+     *   CVGS_OP_REORDER in front.  Any other type: CVGS_ERR_INVALID.
+     * Target.  write.planes2d = host cvgs_image2d[read.batch], one surface per plane, as for PIXEL_2D_BATCH.  data = Y(0,0); step in bytes,
+     *   >= width; uv_offset = bytes from data to the chroma row of luma row 0, 0 = height * step (the meaning it has on the read side: a
+     *   crop of a larger surface at an even origin is a target like any other).  width and height must equal the size the read stage
+     *   produces and must be even (CVGS_ERR_INVALID otherwise, like the NV12 read).
+     * Colour parameters.  write.yuv_params (the int32 that was `reserved` until this kind existed; every other kind ignores it):
+     *   bits 0-3 cvgs_yuv_range, bits 4-7 cvgs_yuv_primaries, bits 8-11 the layout, CVGS_YUV_NV12 or CVGS_YUV_NV21 only
+     *   (CVGS_WRITE_YUV_PARAMS below); all other bits zero.
+     * Arithmetic (the contract: strict fp32, no contraction, every operation rounded once, in this order).  Per pixel:
+     *     y = (Kr*R + Kg*G) + Kb*B;   cb = (B - y) * cu;   cr = (R - y) * cv
+     *   full range:    Y = y,            U = cb + 128,       V = cr + 128
+     *   limited range: Y = y * sy + 16,  U = cb * sc + 128,  V = cr * sc + 128
+     *   Kr, Kg, Kb = the luma weights of BT.601 (0.299, 0.587, 0.114), BT.709 (0.2126, 0.7152, 0.0722), BT.2020 NCL (0.2627, 0.678, 0.0593);
+     *   cu = 0.5 / (1 - Kb), cv = 0.5 / (1 - Kr); sy = 219/255, sc = 224/255 -- all as 6-decimal fp32 literals:
+     *     BT.601  cu 0.564334 cv 0.713267;  BT.709  cu 0.538909 cv 0.635001;  BT.2020  cu 0.531519 cv 0.678150;  sy 0.858824  sc 0.878431
+     *   The luma byte of pixel (x, y) is Y under the CVGS_OP_CAST-to-8U rule: round to nearest even, saturate to 0..255 (NaN -> 0).
+     *   The chroma pair of the 2 x 2 block (bx, by) comes from the four FLOAT U and V values of its pixels, nothing rounded in between:
+     *     Ub = ((U(2bx,2by) + U(2bx+1,2by)) + (U(2bx,2by+1) + U(2bx+1,2by+1))) * 0.25f, Vb the same with V; each rounded by the same rule
+     *   and stored at data + uv_offset + by*step + 2*bx as (Ub, Vb) for NV12, (Vb, Ub) for NV21.
+     * Bytes written.  A plane writes the bytes [0, width) of each of its `height` luma rows and of its height/2 chroma rows, and nothing
+     *   else: row padding stays untouched.  Planes z >= used_planes run the background value through the chain and are written like any other.
+     * Served by cvgs_execute -- read kinds CVGS_READ_PIXEL, CVGS_READ_RESIZE_LINEAR, CVGS_READ_NV12, CVGS_READ_NV12_RESIZE_LINEAR with every
+     *   source type and layout they take, host views or a device plane table, any fp32 program -- and one by one by cvgs_execute_many.
+     *   CVGS_ERR_UNSUPPORTED: CV_64F values, mirrors, warp reads, CVGS_READ_RESIZE_AREA, the descriptor queue, cvgs_circular_update.
+     * Transcoding a surface at its own size with the same range and primaries in and out returns it byte for byte.                       */
+    CVGS_WRITE_NV12 = 6
 } cvgs_write_kind;
+
+/* cvgs_write_desc.yuv_params of a CVGS_WRITE_NV12 chain */
+#define CVGS_WRITE_YUV_PARAMS(range, primaries, layout) (((range) & 15) | (((primaries) & 15) << 4) | (((layout) & 15) << 8))
+#define CVGS_WRITE_YUV_RANGE(p) ((p) & 15)
+#define CVGS_WRITE_YUV_PRIMARIES(p) (((p) >> 4) & 15)
+#define CVGS_WRITE_YUV_LAYOUT(p) (((p) >> 8) & 15)
 
 typedef struct cvgs_write_desc {
     int32_t kind;     /* cvgs_write_kind                                                       */
@@ -310,7 +346,8 @@ typedef struct cvgs_write_desc {
     int32_t step;     /* PIXEL_2D: row pitch in bytes; tensor kinds: ignored (dense)           */
     int32_t planes;   /* tensor kinds: number of images N in the tensor (>= read.batch)        */
     /* SPLIT_2D: host array cvgs_image2d[batch*channels], index z*channels+c.
-     * PIXEL_2D_BATCH: host array cvgs_image2d[batch].                                         */
+     * PIXEL_2D_BATCH: host array cvgs_image2d[batch].
+     * NV12: host array cvgs_image2d[batch], the luma views with their uv_offset.              */
     const cvgs_image2d* planes2d;
     /* Tensor kinds (TENSOR_SPLIT / TENSOR_T_SPLIT / PIXEL_3D) only: n_mirrors (<= CVGS_MAX_MIRRORS) further device
      * tensors of the same shape that receive the SAME values at the same element offsets as `data`, in the same kernel
@@ -320,7 +357,7 @@ typedef struct cvgs_write_desc {
      * cvgs_peer_enable), so no separate all-gather moves the data a second time.  No reference counterpart.        */
     void* const* mirrors;
     int32_t n_mirrors;
-    int32_t reserved;
+    int32_t yuv_params; /* CVGS_WRITE_NV12: CVGS_WRITE_YUV_PARAMS(range, primaries, layout); ignored by every other kind */
 } cvgs_write_desc;
 
 /* ---- the fused chain = one kernel launch --------------------------------------------------- */

@@ -1366,6 +1366,179 @@ int execute_many(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream) {
 
 } // namespace
 
+// ---- CircularTensor: the handle, its slot arithmetic, lowering, write targets and update routes (the C entry points: further down) -------
+struct cvgs_circular_s {
+    int32_t width, height, elem_type, color_planes, batch, order, cp_mode, device;
+    size_t plane_bytes; // one colour plane of one image
+    size_t image_bytes; // color_planes planes
+    uint8_t* out;       // ordered tensor handed to the user (data())
+    uint8_t* ring;      // history: update k lives in slot k % batch, standard [c][y][x] order
+    int64_t count;
+    bool mirrored;      // ring of 2*batch slots, every frame stored twice, data() is a moving window; `out` unused
+    bool capturable;    // CVGS_CIRCULAR_CAPTURABLE: the count lives in `dcount`, updates go through `stage`
+    uint8_t* stage;     // one image
+    uint64_t* dcount;   // device: updates completed
+};
+
+namespace {
+
+// Slot arithmetic.  k_circular.hip (k_circular_dev, k_circular_push<DEV>) restates it on the device from the device-side count: they must agree.
+int circ_new_slot(const cvgs_circular_s* ct) { return ct->order == CVGS_NEWEST_FIRST ? 0 : ct->batch - 1; } // the new frame's slot of the ordered tensor
+int64_t circ_history_slot(const cvgs_circular_s* ct, int64_t k) { // the history slot of update k (k < 0: a slot not written yet, zeros)
+    const int64_t slot = k % ct->batch;
+    return slot < 0 ? slot + ct->batch : slot;
+}
+int64_t circ_mirror_slot(const cvgs_circular_s* ct, int64_t k) { // mirrored ring of 2 * BATCH slots: update k is stored at p and at p + BATCH
+    const int64_t km = circ_history_slot(ct, k);
+    return ct->order == CVGS_NEWEST_FIRST ? ct->batch - 1 - km : km;
+}
+int64_t circ_window_start(const cvgs_circular_s* ct, int64_t count) { // mirrored ring: the slot data() starts at after `count` updates
+    if (count == 0) return 0; // nothing pushed yet: any window is all zeros
+    const int64_t p = circ_mirror_slot(ct, count - 1);
+    return ct->order == CVGS_NEWEST_FIRST ? p : p + 1;
+}
+// the history slot that tensor slot z shows once update k has run: the frame of age z (NewestFirst) or BATCH-1-z (OldestFirst)
+int64_t circ_shown_slot(const cvgs_circular_s* ct, int64_t k, int z) {
+    return circ_history_slot(ct, k - (ct->order == CVGS_NEWEST_FIRST ? z : ct->batch - 1 - z));
+}
+
+// The update's chain lowered against the handle (the only lowering with circular == true).  `placeholder` gives validation a non-null target;
+// every route sets the real ones afterwards (circ_set_targets).  The kernels index with the frame's extent and strides derived from the
+// tensor's: they must be the same.
+int circ_lower(const cvgs_circular_s* ct, cvgs_chain_desc& one, void* placeholder, Lowered& L) {
+    one.write.data = placeholder;
+    one.write.width = ct->width;
+    one.write.height = ct->height;
+    one.write.planes = ct->batch;
+    const int rc = lower(&one, true, L);
+    if (rc) return rc;
+    if (L.out_w != ct->width || L.out_h != ct->height)
+        return fail(CVGS_ERR_INVALID, "the frame produced by the read stage differs from the CircularTensor's plane size");
+    return CVGS_OK;
+}
+
+// Where one frame goes: base pointer, elements from image to image and from colour plane to colour plane.  data == nullptr: no such target.
+struct CircTarget {
+    uint8_t* data = nullptr;
+    int64_t img_stride = 0, ch_stride = 0;
+};
+// Standard layout (ring slots, the staging image, Standard tensors): the planes of one frame together, a packed frame one plane of pixels.
+// Transposed ordered tensor: plane c of slot z is plane c * BATCH + z, and `base` is plane 0 of the frame's slot.
+CircTarget circ_target(const cvgs_circular_s* ct, int wk, uint8_t* base, bool transposed = false) {
+    const int64_t plane = (int64_t)ct->width * ct->height; // elements of one colour plane (packed: pixels)
+    if (transposed) return {base, plane, plane * ct->batch};
+    return wk == CVGS_WRITE_PIXEL_3D ? CircTarget{base, plane, 0} : CircTarget{base, plane * ct->color_planes, plane};
+}
+CircTarget circ_ring_target(const cvgs_circular_s* ct, int wk, int64_t slot) { return circ_target(ct, wk, ct->ring + (size_t)slot * ct->image_bytes); }
+CircTarget circ_tensor_target(const cvgs_circular_s* ct, int wk) { // the new frame's slot of the ordered tensor (the same for every update)
+    const size_t z = (size_t)circ_new_slot(ct);
+    return wk == CVGS_WRITE_TENSOR_T_SPLIT ? circ_target(ct, wk, ct->out + z * ct->plane_bytes, true) : circ_target(ct, wk, ct->out + z * ct->image_bytes);
+}
+// Points a lowered chain at its targets.  Without `second` the fields are what lower() leaves for a chain with one target, so a Lowered
+// that a declined push attempt pointed at two targets goes on to dispatch() as if freshly lowered.
+void circ_set_targets(int wk, WriteArgs& Wa, const CircTarget& first, const CircTarget& second = CircTarget{}) {
+    Wa.kind = wk == CVGS_WRITE_TENSOR_T_SPLIT ? CVGS_WRITE_TENSOR_SPLIT : wk; // (the Transposed order is in the strides)
+    Wa.planes = 1;
+    Wa.data = first.data;
+    Wa.img_stride = first.img_stride;
+    Wa.ch_stride = first.ch_stride;
+    Wa.data2 = second.data;
+    Wa.img_stride2 = second.img_stride;
+    Wa.ch_stride2 = second.ch_stride;
+}
+
+// What the single-launch push (k_circular_push) can take at all; launch_circular_push judges the rest (program class, alignment, job count).
+bool circ_push_eligible(const Lowered& L) { return !L.uses_64f && L.planes.size() == 1 && !L.args.read.table && L.dst_planes.empty(); }
+
+// Capturable handle: nothing that depends on the update count is resolved on the host, so a captured update replays as the NEXT update.
+int circ_update_capturable(cvgs_circular_s* ct, cvgs_chain_desc& one, cvgs_stream_t stream) {
+    const int wk = one.write.kind;
+    CircDev dev{};
+    dev.out = ct->out;
+    dev.ring = ct->ring;
+    dev.stage = ct->stage;
+    dev.count = ct->dcount;
+    dev.plane_bytes = ct->plane_bytes;
+    dev.batch = ct->batch;
+    dev.color_planes = ct->color_planes;
+    dev.order = ct->order;
+    dev.transposed = ct->cp_mode == CVGS_PLANES_TRANSPOSED;
+    dev.mirrored = ct->mirrored;
+    Lowered L; // lowered ONCE: both attempts below differ in the write targets only
+    int rc = circ_lower(ct, one, ct->ring, L);
+    if (rc) return rc;
+    // Per-pixel u8 pushes (the form the reference tests): ONE launch whose kernel reads the device-side count and derives the
+    // new frame's ring slot and every copy job itself -- the traffic of an eager update, no staging image
+    if (circ_push_eligible(L)) {
+        const CircTarget ring = circ_ring_target(ct, wk, 0); // the kernel replaces it: ring slot count % BATCH (mirrored: slots p and p + BATCH)
+        circ_set_targets(wk, L.args.write, ct->mirrored ? ring : circ_tensor_target(ct, wk), ring);
+        const int n_jobs = ct->mirrored ? 0 : (ct->batch - 1) * ct->color_planes;
+        rc = launch_circular_push(L.args, L.planes[0], nullptr, n_jobs, ct->plane_bytes, one.flags, stream, &dev);
+        if (rc < 0) return fail(CVGS_ERR_HIP, "CircularTensor push launch failed");
+        if (rc == 1) return launch_circular_bump(ct->dcount, stream) ? fail(CVGS_ERR_HIP, "CircularTensor count launch failed") : CVGS_OK;
+    }
+    // every other push: the chain writes the new frame into the staging image (standard order), the shift kernel derives every
+    // plane job from the device-side count (k_circular.hip: k_circular_dev), a last kernel advances it
+    circ_set_targets(wk, L.args.write, circ_target(ct, wk, ct->stage));
+    rc = dispatch(&one, L, (hipStream_t)stream, false, nullptr);
+    if (rc) return rc;
+    if (launch_circular_dev(dev, stream)) return fail(CVGS_ERR_HIP, "CircularTensor device-indexed shift launch failed");
+    return CVGS_OK;
+}
+
+// Mirrored ring: ONE pass over the new frame, stored at slot p and at slot p+BATCH of a 2*BATCH ring; nothing is shifted.
+int circ_update_mirrored(cvgs_circular_s* ct, cvgs_chain_desc& one, cvgs_stream_t stream) {
+    const int wk = one.write.kind;
+    Lowered L;
+    const int rc = circ_lower(ct, one, ct->ring, L);
+    if (rc) return rc;
+    const int64_t p = circ_mirror_slot(ct, ct->count);
+    circ_set_targets(wk, L.args.write, circ_ring_target(ct, wk, p), circ_ring_target(ct, wk, p + ct->batch));
+    return dispatch(&one, L, (hipStream_t)stream, false, nullptr);
+}
+
+int circ_update_default(cvgs_circular_s* ct, cvgs_chain_desc& one, cvgs_stream_t stream) {
+    const int wk = one.write.kind;
+    // 1) ONE pass over the new frame writes it twice: into its slot of the ordered tensor and into the history ring (slot = update
+    //    index mod BATCH, always standard plane order).
+    Lowered L;
+    int rc = circ_lower(ct, one, ct->ring, L);
+    if (rc) return rc;
+    circ_set_targets(wk, L.args.write, circ_tensor_target(ct, wk), circ_ring_target(ct, wk, circ_history_slot(ct, ct->count)));
+    // 2) every OLDER frame: history ring -> its new slot of the ordered tensor; never-written history slots are zero.
+    SmallBuf<CopyJob, kMaxCopyJobs> jobs;
+    if (!jobs.resize((size_t)(ct->batch - 1) * ct->color_planes)) return fail(CVGS_ERR_HIP, "out of host memory");
+    size_t n_jobs = 0;
+    for (int z = 0; z < ct->batch; ++z) {
+        if (z == circ_new_slot(ct)) continue;
+        const int64_t src_slot = circ_shown_slot(ct, ct->count, z);
+        for (int c = 0; c < ct->color_planes; ++c) {
+            CopyJob j;
+            j.src = ct->ring + (size_t)src_slot * ct->image_bytes + (size_t)c * ct->plane_bytes;
+            j.dst = ct->cp_mode == CVGS_PLANES_TRANSPOSED ? ct->out + ((size_t)c * ct->batch + z) * ct->plane_bytes
+                                                          : ct->out + ((size_t)z * ct->color_planes + c) * ct->plane_bytes;
+            jobs[n_jobs++] = j;
+        }
+    }
+    // Per-pixel u8 pushes (the form the reference tests) take ONE launch: compute + every copy in the same kernel.
+    // No copy reads the ring slot or writes the tensor slot the compute part fills (ages >= 1 only), so the two parts
+    // are independent inside the launch.
+    if (n_jobs > 0 && (int)n_jobs <= kMaxCopyJobs && circ_push_eligible(L)) {
+        rc = launch_circular_push(L.args, L.planes[0], jobs.data(), (int)n_jobs, ct->plane_bytes, one.flags, stream);
+        if (rc < 0) return fail(CVGS_ERR_HIP, "CircularTensor push launch failed");
+        if (rc == 1) return CVGS_OK;
+    }
+    rc = dispatch(&one, L, (hipStream_t)stream, false, nullptr);
+    if (rc) return rc;
+    for (size_t at = 0; at < n_jobs; at += kMaxCopyJobs) {
+        const int n = (int)std::min<size_t>(kMaxCopyJobs, n_jobs - at);
+        if (launch_plane_copies(jobs.data() + at, n, ct->plane_bytes, stream)) return fail(CVGS_ERR_HIP, "CircularTensor copy launch failed");
+    }
+    return CVGS_OK;
+}
+
+} // namespace
+
 extern "C" {
 
 int cvgs_abi_version(void) { return CVGS_ABI_VERSION; }
@@ -1651,20 +1824,7 @@ int cvgs_warp_table_build_host(const cvgs_warp_table_desc* desc, void* table_out
     return CVGS_OK;
 }
 
-// ---- CircularTensor ------------------------------------------------------------------------------
-struct cvgs_circular_s {
-    int32_t width, height, elem_type, color_planes, batch, order, cp_mode, device;
-    size_t plane_bytes; // one colour plane of one image
-    size_t image_bytes; // color_planes planes
-    uint8_t* out;       // ordered tensor handed to the user (data())
-    uint8_t* ring;      // history: update k lives in slot k % batch, standard [c][y][x] order
-    int64_t count;
-    bool mirrored;      // ring of 2*batch slots, every frame stored twice, data() is a moving window; `out` unused
-    bool capturable;    // CVGS_CIRCULAR_CAPTURABLE: the count lives in `dcount`, updates go through `stage`
-    uint8_t* stage;     // one image
-    uint64_t* dcount;   // device: updates completed
-};
-
+// ---- CircularTensor (the handle and the update routes: in front of this block) ---------------------------------
 int cvgs_circular_create(cvgs_circular_t* out, int32_t width, int32_t height, int32_t elem_type,
                          int32_t color_planes, int32_t batch, int32_t order, int32_t cp_mode, int32_t device_id) {
     return cvgs_circular_create_ex(out, width, height, elem_type, color_planes, batch, order, cp_mode, device_id, 0);
@@ -1761,190 +1921,10 @@ int cvgs_circular_update(cvgs_circular_t ct, const cvgs_chain_desc* chain, cvgs_
         int rc = guard.enter(ct->device);
         if (rc) return rc;
     }
-    if (ct->capturable) {
-        CircDev dev{};
-        dev.out = ct->out;
-        dev.ring = ct->ring;
-        dev.stage = ct->stage;
-        dev.count = ct->dcount;
-        dev.plane_bytes = ct->plane_bytes;
-        dev.batch = ct->batch;
-        dev.color_planes = ct->color_planes;
-        dev.order = ct->order;
-        dev.transposed = ct->cp_mode == CVGS_PLANES_TRANSPOSED;
-        dev.mirrored = ct->mirrored;
-        // Per-pixel u8 pushes (the form the reference tests): ONE launch whose kernel reads the device-side count and derives the
-        // new frame's ring slot and every copy job itself -- the traffic of an eager update, no staging image
-        {
-            Lowered Lp;
-            cvgs_chain_desc onep = one;
-            onep.write.data = ct->ring;
-            onep.write.width = ct->width;
-            onep.write.height = ct->height;
-            onep.write.planes = ct->batch;
-            int rcp = lower(&onep, true, Lp);
-            if (rcp) return rcp;
-            if (Lp.out_w != ct->width || Lp.out_h != ct->height)
-                return fail(CVGS_ERR_INVALID, "the frame produced by the read stage differs from the CircularTensor's plane size");
-            if (!Lp.uses_64f && Lp.planes.size() == 1 && !Lp.args.read.table && Lp.dst_planes.empty()) {
-                const int64_t plane = (int64_t)ct->width * ct->height;
-                const int z_new = ct->order == CVGS_NEWEST_FIRST ? 0 : ct->batch - 1;
-                WriteArgs& Wa = Lp.args.write;
-                Wa.kind = wk == CVGS_WRITE_TENSOR_T_SPLIT ? CVGS_WRITE_TENSOR_SPLIT : wk;
-                Wa.planes = 1;
-                const int64_t std_img = wk == CVGS_WRITE_PIXEL_3D ? plane : plane * ct->color_planes, std_ch = wk == CVGS_WRITE_PIXEL_3D ? 0 : plane;
-                if (ct->mirrored) { // both targets are ring slots the kernel picks from the count
-                    Wa.data = ct->ring;
-                    Wa.img_stride = std_img;
-                    Wa.ch_stride = std_ch;
-                } else if (wk == CVGS_WRITE_TENSOR_T_SPLIT) {
-                    Wa.data = ct->out + (size_t)z_new * ct->plane_bytes;
-                    Wa.img_stride = plane;
-                    Wa.ch_stride = plane * ct->batch;
-                } else {
-                    Wa.data = ct->out + (size_t)z_new * ct->image_bytes;
-                    Wa.img_stride = std_img;
-                    Wa.ch_stride = std_ch;
-                }
-                Wa.data2 = ct->ring; // the kernel replaces it: ring slot count % BATCH (mirrored: slot p + BATCH)
-                Wa.img_stride2 = std_img;
-                Wa.ch_stride2 = std_ch;
-                const int n_jobs = ct->mirrored ? 0 : (ct->batch - 1) * ct->color_planes;
-                rcp = launch_circular_push(Lp.args, Lp.planes[0], nullptr, n_jobs, ct->plane_bytes, one.flags, stream, &dev);
-                if (rcp < 0) return fail(CVGS_ERR_HIP, "CircularTensor push launch failed");
-                if (rcp == 1) {
-                    if (launch_circular_bump(ct->dcount, stream)) return fail(CVGS_ERR_HIP, "CircularTensor count launch failed");
-                    ct->count++;
-                    return CVGS_OK;
-                }
-            }
-        }
-        // every other push: the chain writes the new frame into the staging image (standard order), the shift kernel derives every
-        // plane job from the device-side count (k_circular.hip: k_circular_dev), a last kernel advances it
-        Lowered L;
-        one.write.data = ct->stage;
-        one.write.width = ct->width;
-        one.write.height = ct->height;
-        one.write.planes = ct->batch;
-        int rc = lower(&one, true, L);
-        if (rc) return rc;
-        if (L.out_w != ct->width || L.out_h != ct->height)
-            return fail(CVGS_ERR_INVALID, "the frame produced by the read stage differs from the CircularTensor's plane size");
-        const int64_t plane = (int64_t)ct->width * ct->height;
-        WriteArgs& Wa = L.args.write;
-        Wa.kind = wk == CVGS_WRITE_TENSOR_T_SPLIT ? CVGS_WRITE_TENSOR_SPLIT : wk;
-        Wa.planes = 1;
-        Wa.data = ct->stage;
-        Wa.data2 = nullptr;
-        Wa.img_stride = wk == CVGS_WRITE_PIXEL_3D ? plane : plane * ct->color_planes;
-        Wa.ch_stride = wk == CVGS_WRITE_PIXEL_3D ? 0 : plane;
-        rc = dispatch(&one, L, (hipStream_t)stream, false, nullptr);
-        if (rc) return rc;
-        if (launch_circular_dev(dev, stream)) return fail(CVGS_ERR_HIP, "CircularTensor device-indexed shift launch failed");
-        ct->count++; // calls made (captured ones count once); the device-side count is the authority (cvgs_circular_updates)
-        return CVGS_OK;
-    }
-    if (ct->mirrored) {
-        // ONE pass over the new frame, stored at slot p and at slot p+BATCH of a 2*BATCH ring; nothing is shifted.
-        // OldestFirst: p = k mod B, window starts at p+1.  NewestFirst: p = B-1 - k mod B, window starts at p.
-        Lowered L;
-        one.write.data = ct->ring;
-        one.write.width = ct->width;
-        one.write.height = ct->height;
-        one.write.planes = ct->batch;
-        int rc = lower(&one, true, L);
-        if (rc) return rc;
-        if (L.out_w != ct->width || L.out_h != ct->height)
-            return fail(CVGS_ERR_INVALID, "the frame produced by the read stage differs from the CircularTensor's plane size");
-        const int64_t km = ct->count % ct->batch;
-        const int64_t p = ct->order == CVGS_NEWEST_FIRST ? ct->batch - 1 - km : km;
-        const int64_t plane = (int64_t)ct->width * ct->height;
-        WriteArgs& Wa = L.args.write;
-        Wa.planes = 1;
-        Wa.data = ct->ring + (size_t)p * ct->image_bytes;
-        Wa.data2 = ct->ring + (size_t)(p + ct->batch) * ct->image_bytes;
-        Wa.img_stride = Wa.img_stride2 = wk == CVGS_WRITE_PIXEL_3D ? plane : plane * ct->color_planes;
-        Wa.ch_stride = Wa.ch_stride2 = wk == CVGS_WRITE_PIXEL_3D ? 0 : plane;
-        rc = dispatch(&one, L, (hipStream_t)stream, false, nullptr);
-        if (rc) return rc;
-        ct->count++;
-        return CVGS_OK;
-    }
-    // 1) ONE pass over the new frame writes it twice: into the history ring (slot = update index mod BATCH, always
-    //    standard plane order) and into its slot of the ordered tensor (slot 0 NewestFirst / BATCH-1 OldestFirst).
-    const int64_t slot = ct->count % ct->batch;
-    const int z_new = ct->order == CVGS_NEWEST_FIRST ? 0 : ct->batch - 1;
-    Lowered L;
-    one.write.data = ct->ring; // placeholder so that validation sees a non-null target
-    one.write.width = ct->width;
-    one.write.height = ct->height;
-    one.write.planes = ct->batch;
-    int rc = lower(&one, true, L);
-    if (rc) return rc;
-    // the kernels index with the frame's extent and strides derived from the tensor's: they must be the same
-    if (L.out_w != ct->width || L.out_h != ct->height)
-        return fail(CVGS_ERR_INVALID, "the frame produced by the read stage differs from the CircularTensor's plane size");
-    {
-        WriteArgs& Wa = L.args.write;
-        const int esz = depth_bytes(CVGS_TYPE_DEPTH(one.write.dst_type));
-        const int64_t plane = (int64_t)ct->width * ct->height; // elements of one colour plane (packed: pixels)
-        Wa.kind = wk == CVGS_WRITE_TENSOR_T_SPLIT ? CVGS_WRITE_TENSOR_SPLIT : wk;
-        Wa.planes = 1;
-        // primary: the ordered tensor
-        if (wk == CVGS_WRITE_TENSOR_T_SPLIT) {
-            Wa.data = ct->out + (size_t)z_new * ct->plane_bytes;
-            Wa.img_stride = plane;
-            Wa.ch_stride = plane * ct->batch;
-        } else {
-            Wa.data = ct->out + (size_t)z_new * ct->image_bytes;
-            Wa.img_stride = wk == CVGS_WRITE_PIXEL_3D ? plane : plane * ct->color_planes;
-            Wa.ch_stride = wk == CVGS_WRITE_PIXEL_3D ? 0 : plane;
-        }
-        // secondary: the ring slot, standard order
-        Wa.data2 = ct->ring + (size_t)slot * ct->image_bytes;
-        Wa.img_stride2 = wk == CVGS_WRITE_PIXEL_3D ? plane : plane * ct->color_planes;
-        Wa.ch_stride2 = wk == CVGS_WRITE_PIXEL_3D ? 0 : plane;
-        (void)esz;
-    }
-    // 2) every OLDER frame: history ring -> its new slot of the ordered tensor.  Slot z shows the frame of age z
-    //    (NewestFirst) or BATCH-1-z (OldestFirst); never-written history slots are zero.
-    SmallBuf<CopyJob, kMaxCopyJobs> jobs;
-    if (!jobs.resize((size_t)(ct->batch - 1) * ct->color_planes)) return fail(CVGS_ERR_HIP, "out of host memory");
-    size_t n_jobs = 0;
-    for (int z = 0; z < ct->batch; ++z) {
-        if (z == z_new) continue;
-        const int64_t age = ct->order == CVGS_NEWEST_FIRST ? z : ct->batch - 1 - z;
-        int64_t src_slot = (ct->count - age) % ct->batch;
-        if (src_slot < 0) src_slot += ct->batch;
-        for (int c = 0; c < ct->color_planes; ++c) {
-            CopyJob j;
-            j.src = ct->ring + (size_t)src_slot * ct->image_bytes + (size_t)c * ct->plane_bytes;
-            j.dst = ct->cp_mode == CVGS_PLANES_TRANSPOSED ? ct->out + ((size_t)c * ct->batch + z) * ct->plane_bytes
-                                                          : ct->out + ((size_t)z * ct->color_planes + c) * ct->plane_bytes;
-            jobs[n_jobs++] = j;
-        }
-    }
-    // Per-pixel u8 pushes (the form the reference tests) take ONE launch: compute + every copy in the same kernel.
-    // No copy reads the ring slot or writes the tensor slot the compute part fills (ages >= 1 only), so the two parts
-    // are independent inside the launch.
-    bool done = false;
-    if (n_jobs > 0 && (int)n_jobs <= kMaxCopyJobs && !L.uses_64f && L.planes.size() == 1 && !L.args.read.table &&
-        L.dst_planes.empty()) {
-        rc = launch_circular_push(L.args, L.planes[0], jobs.data(), (int)n_jobs, ct->plane_bytes, one.flags, stream);
-        if (rc < 0) return fail(CVGS_ERR_HIP, "CircularTensor push launch failed");
-        done = rc == 1;
-    }
-    if (!done) {
-        rc = dispatch(&one, L, (hipStream_t)stream, false, nullptr);
-        if (rc) return rc;
-        for (size_t at = 0; at < n_jobs; at += kMaxCopyJobs) {
-            const int n = (int)std::min<size_t>(kMaxCopyJobs, n_jobs - at);
-            rc = launch_plane_copies(jobs.data() + at, n, ct->plane_bytes, stream);
-            if (rc) return fail(CVGS_ERR_HIP, "CircularTensor copy launch failed");
-        }
-    }
-    ct->count++;
-    return CVGS_OK;
+    const int rc = ct->capturable ? circ_update_capturable(ct, one, stream)
+                                  : ct->mirrored ? circ_update_mirrored(ct, one, stream) : circ_update_default(ct, one, stream);
+    if (rc == CVGS_OK) ct->count++; // calls made (captured ones count once); a capturable handle's device-side count is the authority (cvgs_circular_updates)
+    return rc;
 }
 
 // capturable handles: the number of updates that have RUN (graph replays included) is device state
@@ -1960,11 +1940,7 @@ static int64_t circular_count(cvgs_circular_t ct) {
 void* cvgs_circular_data(cvgs_circular_t ct) {
     if (!ct) return nullptr;
     if (!ct->mirrored) return ct->out;
-    const int64_t count = circular_count(ct);
-    if (count == 0) return ct->ring; // nothing pushed yet: any window is all zeros
-    const int64_t km = (count - 1) % ct->batch;
-    const int64_t start = ct->order == CVGS_NEWEST_FIRST ? ct->batch - 1 - km : km + 1;
-    return ct->ring + (size_t)start * ct->image_bytes;
+    return ct->ring + (size_t)circ_window_start(ct, circular_count(ct)) * ct->image_bytes;
 }
 size_t cvgs_circular_bytes(cvgs_circular_t ct) { return ct ? ct->image_bytes * (size_t)ct->batch : 0; }
 int64_t cvgs_circular_updates(cvgs_circular_t ct) { return ct ? circular_count(ct) : -1; }

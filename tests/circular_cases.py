@@ -19,6 +19,7 @@ Case = collections.namedtuple("Case", "name handle mirrored order layout depth c
 DEPTHS = {"32f": cvgs.CV_32F, "16f": cvgs.CV_16F, "16bf": capi.DEPTH_16BF, "8u": cvgs.CV_8U, "64f": cvgs.CV_64F}
 ELEM_BYTES = {"32f": 4, "16f": 2, "16bf": 2, "8u": 1, "64f": 8}
 RESIZE_SRC = (53, 31)  # (width, height) of the frames a resize push reads
+MAX_COPY_JOBS = 64  # kMaxCopyJobs (cvgs_device.h): launch_circular_push declines more, launch_plane_copies takes them in chunks of it
 MUL, SUB, DIV, ADD = [0.3, 0.31, 0.29, 0.5], [0.4, 0.45, 0.5, 0.1], [0.25, 0.22, 0.23, 0.2], [3.25, 1.5, 0.75, 2.0]
 
 
@@ -101,7 +102,8 @@ def ring(case):
 def route(case):
     """"push": the single-launch k_circular_push (DEV = capturable);  "stage": chain -> staging image, then k_circular_dev;
     "chain+copy": chain kernel, then k_plane_copy;  "chain": the chain kernel alone (default mirrored rings, BATCH 1)."""
-    push_ok = case.push != "rs" and case.depth in ("32f", "16f", "16bf") and plane_bytes(case) % 16 == 0
+    jobs = 0 if case.mirrored else (case.batch - 1) * color_planes(case)  # the copy jobs a push launch would carry
+    push_ok = case.push != "rs" and case.depth in ("32f", "16f", "16bf") and plane_bytes(case) % 16 == 0 and jobs <= MAX_COPY_JOBS
     if case.handle == "dev":
         return "push" if push_ok else "stage"
     if case.mirrored or case.batch == 1:
@@ -202,5 +204,10 @@ for _h in ("def", "dev"):
     add("packed_{r}_{h}", _h, True, "of", "pk", "32f", 3, 3, 40, 24, "px_mad")
     add("packed_{r}_{h}", _h, True, "nf", "pk", "16f", 4, 2, 37, 23, "rs")
     add("packed_{h}_copy1", _h, False, "nf", "pk", "8u", 3, 3, 37, 23, "rs")          # 2553 bytes
+    # either side of the push launch's 64 copy jobs, by a per-pixel push that is eligible in every other respect: BATCH 22 = 63 jobs (push),
+    # BATCH 23 = 66 (capturable: stage-then-shift; default: the chain kernel, then copy launches of 64 + 2 jobs)
+    add("jobs63_{r}_{h}", _h, False, "nf", "std", "32f", 3, 22, 40, 24, "px_msd")
+    add("jobs66_{r}_{h}", _h, False, "of", "std", "32f", 3, 23, 40, 24, "px_msd")
 
-assert len(CASES) <= 80, len(CASES)
+BESIDE_THE_JOB_LIMIT = [n for n in CASES if n.startswith("jobs6")]  # on the GPU: subtests of one item (tests/test_gpu_circular_model.py)
+assert len(CASES) <= 80 and len(BESIDE_THE_JOB_LIMIT) == 4, len(CASES)

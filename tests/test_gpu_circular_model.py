@@ -91,7 +91,28 @@ class Run:
         return seen
 
 
-@pytest.mark.parametrize("name", [n for n, c in CC.CASES.items() if c.handle == "def"])
+def _items(handle):
+    """the cases that are test items of this module; CC.BESIDE_THE_JOB_LIMIT run as subtests of tests/test_zz_gpu_ring.py (the GPU suite's
+    list of tests is kept from growing: tests/test_gpu_area.py says how), through the same two functions"""
+    return [n for n, c in CC.CASES.items() if c.handle == handle and n not in CC.BESIDE_THE_JOB_LIMIT]
+
+
+def run_cases_beside_the_job_limit(device, subtests):
+    """Only a mismatch (AssertionError) lets the item go on to its next case: whatever else ends a case ends the item."""
+    stopped = []
+    for name in CC.BESIDE_THE_JOB_LIMIT:
+        with subtests.test(case=name):
+            assert not stopped, "not started: an earlier case ended with %s" % stopped[0]
+            try:
+                (test_default_handle_within_the_model if CC.CASES[name].handle == "def" else test_capturable_handle_within_the_model)(device, name)
+            except AssertionError:
+                raise
+            except BaseException as e:
+                stopped.append(repr(e)[:300])
+                raise
+
+
+@pytest.mark.parametrize("name", _items("def"))
 def test_default_handle_within_the_model(device, name):
     case = CC.CASES[name]
     n = max(case.batch + 3, 3 * case.batch) if case.mirrored else case.batch + 3
@@ -108,7 +129,7 @@ def test_default_handle_within_the_model(device, name):
         run.ct.release()
 
 
-@pytest.mark.parametrize("name", [n for n, c in CC.CASES.items() if c.handle == "dev"])
+@pytest.mark.parametrize("name", _items("dev"))
 def test_capturable_handle_within_the_model(device, name):
     import torch
     case = CC.CASES[name]

@@ -893,6 +893,94 @@ struct Upload {
     ~Upload() { done(false); }
 };
 
+// Where the plane descriptors of one cvgs_execute_many tick live while its launch reads them.  Four carriers, chosen once (plan_tick, begin):
+//   device_tables  the callers' own device tables: nothing is held
+//   kernarg        segments AND planes travel in the kernel arguments (KernArgsManyInline: nothing to recycle, capturable); the planes are
+//                  gathered in a per-thread vector
+//   host_table     a slot of the stream's ring, recycled through the launch's progress word (ManyPool; ms->mu is held from begin to the launch:
+//                  sequence numbers reach the stream in order) -- or, when the ring has no room or CVGS_MANY_PROGRESS_WORD=0, the
+//                  event-tracked descriptor scratch (Upload, which refuses a capturing stream)
+// Whatever begin() took is given back by finish(), at the latest by the destructor: a tick that is refused or fails after begin() leaks nothing.
+enum class TickCarrier { device_tables, kernarg, host_table };
+struct TickTable {
+    int begin(TickCarrier carrier, size_t bytes, hipStream_t s) {
+        stream = s;
+        if (carrier == TickCarrier::device_tables) return 0;
+        if (carrier == TickCarrier::kernarg) {
+            static thread_local std::vector<PlaneParams> planes; // every chain's planes, in chain order
+            planes.clear();
+            args = &planes;
+            return 0;
+        }
+        static const bool progress_word = [] { const char* e = getenv("CVGS_MANY_PROGRESS_WORD"); return e ? e[0] != '0' : true; }();
+        if (progress_word && (ms = many_pool().get(s, stream_device(s))) != nullptr) {
+            ms_lock = std::unique_lock<std::mutex>(ms->mu);
+            mslot = many_pool().acquire(ms, bytes);
+            if (mslot) return 0;
+            ms_lock.unlock();
+            ms = nullptr;
+        }
+        return up.begin(bytes, s);
+    }
+    // chain L's planes go into the carrier; returns what the chain's ManySeg::table holds: a device address (the chain's own table, the ring,
+    // the scratch) or, for the kernel-argument block, the chain's first index into the block's planes
+    const PlaneParams* put(const Lowered& L) {
+        const size_t bytes = L.planes.size() * sizeof(PlaneParams);
+        if (args) {
+            const size_t first = args->size();
+            args->insert(args->end(), L.planes.data(), L.planes.data() + L.planes.size());
+            return (const PlaneParams*)(uintptr_t)first;
+        }
+        if (mslot) {
+            std::memcpy((uint8_t*)mslot->host + ms_used, L.planes.data(), bytes);
+            const PlaneParams* at = (const PlaneParams*)((uint8_t*)mslot->host_dev + ms_used);
+            ms_used += (bytes + 15) & ~(size_t)15;
+            return at;
+        }
+        if (up.slot >= 0) return (const PlaneParams*)up.put(L.planes.data(), bytes);
+        return L.args.read.table;
+    }
+    // the kernel-argument carrier's planes (nullptr / 0 for every other carrier)
+    const PlaneParams* planes() const { return args ? args->data() : nullptr; }
+    int n_planes() const { return args ? (int)args->size() : 0; }
+    // every chain is in: completes the staged copy (scratch, CVGS_SCRATCH_ZEROCOPY=0) and tells the launch how the carrier learns that it ran
+    int arm(LaunchCtx& ctx) {
+        if (up.slot >= 0) {
+            const int rc = up.flush();
+            if (rc) return rc;
+        }
+        ctx.stop_event = up.stop_event;
+        if (mslot) { // this launch is number next_seq of its stream: when it starts, number next_seq - 1 has finished
+            ctx.done_word = ms->done_dev;
+            ctx.done_value = ms->next_seq - 1;
+        }
+        return 0;
+    }
+    // launched: the kernel that reads the carrier has been enqueued with `ctx`; otherwise nothing was enqueued
+    void finish(bool launched, const LaunchCtx* ctx = nullptr) {
+        if (mslot && launched) {
+            if (ctx->done_word_taken) mslot->seq = ms->next_seq++;
+            else { // (a launch site that does not carry the word: make the slot safe the slow way -- not expected)
+                (void)hipStreamSynchronize(stream);
+                mslot->seq = 0;
+            }
+        }
+        mslot = nullptr;
+        if (ms_lock.owns_lock()) ms_lock.unlock();
+        up.done(launched, launched && ctx->stop_event_taken);
+        args = nullptr;
+    }
+    ~TickTable() { finish(false); }
+private:
+    hipStream_t stream = nullptr;
+    std::vector<PlaneParams>* args = nullptr;
+    ManyStream* ms = nullptr;
+    ManySlot* mslot = nullptr;
+    std::unique_lock<std::mutex> ms_lock;
+    size_t ms_used = 0;
+    Upload up;
+};
+
 // The resize kernel family of a decode-side chain, by its layout: planar 4:4:4 (k_yuv444.hip) and packed 4:2:2 (k_yuv422.hip) serve any
 // plane width; the 4:2:0 layouts are K4's (k_nv12.hip), which wants min_width >= 4.  1 launched / 0 not eligible / < 0 error.
 int launch_yuv_resize(const ChainArgs& c, const PlaneParams* inline_planes, int n_inline, int min_width, LaunchCtx& ctx, bool dry_run, LaunchInfo* info,
@@ -907,6 +995,12 @@ bool yuv_planes_eligible(int layout, const PlaneParams* planes, int n, int dst_w
     for (int i = 0; i < n; ++i)
         if (planes[i].x1 != 0 || planes[i].y1 != 0 || planes[i].x2 != dst_w - 1 || planes[i].y2 != dst_h - 1) return false;
     return true;
+}
+// the narrowest of the planes that are read (default-value planes carry no source)
+int min_read_width(const PlaneParams* planes, int n, int used) {
+    int min_w = 1 << 30;
+    for (int i = 0; i < n && i < used; ++i) min_w = planes[i].w < min_w ? planes[i].w : min_w;
+    return min_w;
 }
 
 int dispatch(const cvgs_chain_desc* ch, Lowered& L, hipStream_t stream, bool dry_run, LaunchInfo* info) {
@@ -926,11 +1020,8 @@ int dispatch(const cvgs_chain_desc* ch, Lowered& L, hipStream_t stream, bool dry
         LaunchCtx probe(stream);
         probe.mirrors = L.mirrors;
         big_inline = launch_k1(L.args, L.planes.data(), (int)L.planes.size(), probe, true, nullptr) == 1;
-        if (!big_inline && !has_mirrors && is_nv12(L.args.read.kind)) { // K4: crops of a decoder surface into a planar tensor
-            int min_w = 1 << 30;
-            for (size_t i = 0; i < L.planes.size() && (int)i < L.args.read.used; ++i) min_w = L.planes[i].w < min_w ? L.planes[i].w : min_w;
-            big_inline = launch_yuv_resize(L.args, L.planes.data(), (int)L.planes.size(), min_w, probe, true, nullptr) == 1;
-        }
+        if (!big_inline && !has_mirrors && is_nv12(L.args.read.kind)) // K4: crops of a decoder surface into a planar tensor
+            big_inline = launch_yuv_resize(L.args, L.planes.data(), (int)L.planes.size(), min_read_width(L.planes.data(), (int)L.planes.size(), L.args.read.used), probe, true, nullptr) == 1;
     }
     const bool up_src = warp ? (int)L.warp_planes.size() > (L.uses_64f ? kInlineWarp64 : kInlineWarp)
                              : (!L.args.read.table && (int)L.planes.size() > inline_cap && !big_inline);
@@ -1009,8 +1100,7 @@ int dispatch(const cvgs_chain_desc* ch, Lowered& L, hipStream_t stream, bool dry
         if (big_inline && (has_mirrors || !is_nv12(L.args.read.kind)))
             return fail(CVGS_ERR_HIP, "internal: K1 refused a chain its dry run accepted"); // only K1 / K4 take > 64 inline planes
         if (!has_mirrors) { // only K1 and the interpreted kernel write mirrors
-            int min_w = 1 << 30; // over the planes that are read (default-value planes carry no source)
-            for (int i = 0; i < n_inline && i < L.args.read.used; ++i) min_w = inline_planes[i].w < min_w ? inline_planes[i].w : min_w;
+            const int min_w = min_read_width(inline_planes, n_inline, L.args.read.used);
             if (up_src && is_nv12(L.args.read.kind) && L.args.read.used == L.args.read.batch &&
                 yuv_planes_eligible(L.args.read.yuv_layout, L.planes.data(), (int)L.planes.size(), L.args.read.dst_w, L.args.read.dst_h)) {
                 // more than 64 crops of a decoder surface: K4 reads the staged table as ONE segment of its fused-chain form
@@ -1158,201 +1248,141 @@ bool chains_independent(const cvgs_chain_desc* const* chains, int n) {
     return true;
 }
 
-// n chains of the thread-fused POINTWISE shape in one launch (round 6; the reference's batched per-pixel chains, tests/batchread/
-// test_batchread_x_write3D.cu:92-96: BATCH crops -> convertTo -> subtract -> divide -> tensor, launch-bound at 4 us for 50 crops of 60 x 120):
-// per-pixel reads of u8 planes of ONE size, host descriptors, a dense fp32 target per chain.  1 launched / 0 not this shape / < 0 error.
-int pointwise_many(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream) {
-    if (n < 2 || n > CVGS_MAX_CHAINS) return 0;
+// A TICK: n chains of one shape in ONE launch.  Three kernel families take one:
+//   pointwise  per-pixel reads of u8 planes of ONE size, host descriptors, a dense fp32 target per chain (round 6; the reference's batched per-pixel
+//              chains, tests/batchread/test_batchread_x_write3D.cu:92-96: BATCH crops -> convertTo -> subtract -> divide -> tensor, launch-bound
+//              at 4 us for 50 crops of 60 x 120)
+//   k1, k4     a resize of pixels (K1) or of decoder surfaces (K4) into a planar tensor
+// plan_tick answers from the descriptors alone; what only the LOWERED chains show is found by launch_tick, which then gives up before anything is enqueued.
+enum class TickFamily { none, pointwise, k1, k4 };
+struct TickPlan {
+    TickFamily family = TickFamily::none;
+    TickCarrier carrier = TickCarrier::kernarg;
     size_t total_planes = 0;
     int max_batch = 0;
+};
+// whatever the one-by-one path would serve must not fail because the chains happen to share a shape.
+//  * host descriptors under stream capture: a staged table is not capturable; one by one, chains of <= 64 planes travel in kernel
+//    arguments and ARE capturable;
+//  * a batch beyond the grid's y range;
+//  * chains that are not independent (one writes where another writes or reads): the fused launch runs them concurrently,
+//    n sequential cvgs_execute calls would not -- keep the sequential meaning.
+TickPlan plan_tick(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream) {
+    const TickPlan none;
+    if (n < 2 || n > CVGS_MAX_CHAINS) return none;
+    const cvgs_chain_desc& c0 = chains[0];
+    TickPlan plan;
+    plan.family = c0.read.kind == CVGS_READ_PIXEL ? TickFamily::pointwise
+                : c0.read.kind == CVGS_READ_RESIZE_LINEAR ? TickFamily::k1
+                : c0.read.kind == CVGS_READ_NV12_RESIZE_LINEAR ? TickFamily::k4 : TickFamily::none;
+    if (plan.family == TickFamily::none) return none;
+    const bool pw = plan.family == TickFamily::pointwise;
+    const bool tables = (c0.read.flags & CVGS_READ_FLAG_TABLE_ON_DEVICE) != 0;
+    if (tables && plan.family != TickFamily::k1) return none; // per-pixel reads and K4's per-plane preconditions want the planes on the host
+    int min_batch = 1;
     const cvgs_chain_desc* ptrs[CVGS_MAX_CHAINS];
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < n; ++i) { // one shape (same_shape: kind, program, target extent), one descriptor form; the planes counted
         const cvgs_chain_desc& c = chains[i];
-        if (c.read.kind != CVGS_READ_PIXEL || (c.flags & (CVGS_CHAIN_FORCE_GENERIC | CVGS_CHAIN_NO_THREAD_FUSION)) || (c.read.flags & CVGS_READ_FLAG_TABLE_ON_DEVICE) ||
-            (c.write.kind != CVGS_WRITE_TENSOR_SPLIT && c.write.kind != CVGS_WRITE_TENSOR_T_SPLIT && c.write.kind != CVGS_WRITE_PIXEL_3D) ||
-            c.read.batch < 1 || c.read.batch > 65535 || !same_shape(chains[0], c))
-            return 0;
-        total_planes += (size_t)c.read.batch;
-        max_batch = std::max(max_batch, (int)c.read.batch);
+        const int wk = c.write.kind;
+        if ((c.flags & (pw ? CVGS_CHAIN_FORCE_GENERIC | CVGS_CHAIN_NO_THREAD_FUSION : CVGS_CHAIN_FORCE_GENERIC)) ||
+            (wk != CVGS_WRITE_TENSOR_SPLIT && wk != CVGS_WRITE_TENSOR_T_SPLIT && !(pw && wk == CVGS_WRITE_PIXEL_3D)) || !same_shape(c0, c) ||
+            ((c.read.flags ^ c0.read.flags) & CVGS_READ_FLAG_TABLE_ON_DEVICE) != 0)
+            return none;
+        plan.total_planes += (size_t)(c.read.batch > 0 ? c.read.batch : 0);
+        plan.max_batch = std::max(plan.max_batch, (int)c.read.batch);
+        min_batch = std::min(min_batch, (int)c.read.batch);
         ptrs[i] = &c;
     }
-    if (total_planes > (size_t)cvgs::kManyInlineLarge || (int64_t)n * max_batch > 65535) return 0;
-    if (!chains_independent(ptrs, n)) return 0; // fused chains run concurrently: keep the sequential meaning of dependent ones
+    // host-described K1 chains of u8 pixels with 3 / 4 channels, K4 chains of interleaved chroma / packed 4:2:2 / planar 4:4:4, pointwise chains:
+    // at most kManyInlineLarge planes in all travel in the kernel arguments (cvgs_device.h: KernArgsManyInline)
+    static const bool inline_ok = [] { const char* e = getenv("CVGS_MANY_INLINE"); return e ? e[0] != '0' : true; }();
+    const bool k1_u8 = plan.family == TickFamily::k1 && CVGS_TYPE_CN(c0.read.src_type) >= 3 && CVGS_TYPE_DEPTH(c0.read.src_type) == CVGS_DEPTH_8U;
+    const bool k4_il = plan.family == TickFamily::k4 &&
+                       (c0.read.yuv_layout == CVGS_YUV_NV12 || c0.read.yuv_layout == CVGS_YUV_NV21 || c0.read.yuv_layout == CVGS_YUV_P010 ||
+                        is_yuv422(c0.read.yuv_layout) || is_yuv444(c0.read.yuv_layout));
+    if (tables) plan.carrier = TickCarrier::device_tables;
+    else if ((pw || (inline_ok && (k1_u8 || k4_il))) && plan.total_planes <= (size_t)cvgs::kManyInlineLarge) plan.carrier = TickCarrier::kernarg;
+    else if (pw) return none; // (the pointwise tick has no table form)
+    else plan.carrier = TickCarrier::host_table;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (plan.carrier == TickCarrier::host_table && hipStreamIsCapturing(stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return none;
+    if (min_batch < 1 || plan.max_batch > 65535 || (pw && (int64_t)n * plan.max_batch > 65535)) return none;
+    if (!chains_independent(ptrs, n)) return none;
+    return plan;
+}
+
+// Would the family's fast kernel take the tick's shape?  A dry run (nothing is enqueued, nothing uploaded) of chain 0 as ONE segment of a table
+// launch, whatever carrier the tick will use: K1 and K4 ask the same of a table launch and of an argument-block launch of the shapes plan_tick admits.
+bool tick_kernel_takes(TickFamily family, const Lowered& L0, hipStream_t stream) {
+    if (L0.int_arith) return false; // integer-typed arithmetic: the interpreted kernel, chain by chain
+    ChainArgs probe = L0.args;
+    probe.read.table = (const PlaneParams*)(uintptr_t)16;
+    const ManySeg one{probe.read.table, probe.write.data, probe.read.batch, probe.read.used};
+    LaunchCtx pctx(stream);
+    pctx.segs = &one;
+    pctx.n_segs = 1;
+    if (family == TickFamily::k4) return launch_yuv_resize(probe, nullptr, 0, 1 << 30, pctx, true, nullptr) == 1; // K4 checks its planes on the host
+    return launch_k1(probe, nullptr, 0, pctx, true, nullptr) == 1;
+}
+// Can lowered chain L ride in the family's tick with chain 0 (L0)?
+bool tick_chain_fits(TickFamily family, const Lowered& L, const Lowered& L0) {
+    if (family == TickFamily::k4) // e.g. a 2-pixel-wide crop: the one-by-one path sends that chain to the interpreted kernel
+        return L.args.read.used == L.args.read.batch &&
+               yuv_planes_eligible(L.args.read.yuv_layout, L.planes.data(), (int)L.planes.size(), L.args.read.dst_w, L.args.read.dst_h);
+    if (family != TickFamily::pointwise) return true;
+    if (L.int_arith || L.uses_64f || L.mirrors.n > 0 || !L.dst_planes.empty() || (int)L.planes.size() != L.args.read.batch) return false;
+    // one plane size for the whole tick (the grid's x / y extent), and it is the target's
+    if (L.args.read.dst_w != L0.args.read.dst_w || L.args.read.dst_h != L0.args.read.dst_h) return false;
+    for (size_t k = 0; k < L.planes.size() && (int)k < L.args.read.used; ++k)
+        if (L.planes[k].w != L0.args.read.dst_w || L.planes[k].h != L0.args.read.dst_h) return false;
+    return true;
+}
+
+// The planned tick: 1 launched / 0 not a fused launch after all (nothing was enqueued, and `table` has given back what it took) / < 0 error.
+int launch_tick(const cvgs_chain_desc* chains, int32_t n, const TickPlan& plan, hipStream_t stream) {
+    const bool pw = plan.family == TickFamily::pointwise, k4 = plan.family == TickFamily::k4;
     ManySeg segs[CVGS_MAX_CHAINS];
-    static thread_local std::vector<PlaneParams> planes;
-    planes.clear();
-    Lowered L0;
-    for (int i = 0; i < n; ++i) {
+    TickTable table;
+    Lowered L0; // the shared read / program / write arguments come from chain 0
+    for (int i = 0; i < n; ++i) { // (one chain at a time: a Lowered holds 320 inline planes)
         Lowered Li;
         Lowered& L = i == 0 ? L0 : Li;
-        const int rc = lower(&chains[i], false, L);
+        int rc = lower(&chains[i], false, L);
         if (rc) return rc; // nothing enqueued yet
-        if (L.int_arith || L.uses_64f || L.mirrors.n > 0 || !L.dst_planes.empty() || (int)L.planes.size() != L.args.read.batch) return 0;
-        // one plane size for the whole tick (the grid's x / y extent), and it is the target's
-        if (L.args.read.dst_w != L0.args.read.dst_w || L.args.read.dst_h != L0.args.read.dst_h) return 0;
-        for (size_t k = 0; k < L.planes.size() && (int)k < L.args.read.used; ++k)
-            if (L.planes[k].w != L0.args.read.dst_w || L.planes[k].h != L0.args.read.dst_h) return 0;
-        segs[i] = ManySeg{(const PlaneParams*)(uintptr_t)planes.size(), L.args.write.data, L.args.read.batch, L.args.read.used};
-        planes.insert(planes.end(), L.planes.data(), L.planes.data() + L.planes.size());
+        if (i == 0) {
+            if (!pw && !tick_kernel_takes(plan.family, L0, stream)) return 0; // (the pointwise kernel is asked below, with the planes it will get)
+            rc = table.begin(plan.carrier, plan.total_planes * sizeof(PlaneParams) + 16 * (size_t)n, stream);
+            if (rc) return rc;
+        }
+        if (!tick_chain_fits(plan.family, L, L0)) return 0;
+        segs[i] = ManySeg{table.put(L), L.args.write.data, L.args.read.batch, L.args.read.used};
     }
     ChainArgs c = L0.args;
-    c.read.batch = max_batch;
-    if (launch_pointwise_many(c, planes.data(), (int)planes.size(), segs, n, max_batch, chains[0].flags, stream, true) != 1) return 0;
-    const int rc = launch_pointwise_many(c, planes.data(), (int)planes.size(), segs, n, max_batch, chains[0].flags, stream, false);
-    if (rc < 0) return fail(CVGS_ERR_HIP, "fused pointwise kernel launch failed");
-    return rc;
+    c.read.batch = plan.max_batch;
+    if (pw) {
+        if (launch_pointwise_many(c, table.planes(), table.n_planes(), segs, n, plan.max_batch, chains[0].flags, stream, true) != 1) return 0;
+        const int rc = launch_pointwise_many(c, table.planes(), table.n_planes(), segs, n, plan.max_batch, chains[0].flags, stream, false);
+        if (rc < 0) return fail(CVGS_ERR_HIP, "fused pointwise kernel launch failed");
+        return rc;
+    }
+    LaunchCtx ctx(stream);
+    ctx.segs = segs;
+    ctx.n_segs = n;
+    int rc = table.arm(ctx);
+    if (rc) return rc;
+    if (table.n_planes() > cvgs::kManyInlineLarge) return fail(CVGS_ERR_INVALID, "inline tick: more planes than counted");
+    c.read.table = plan.carrier == TickCarrier::kernarg ? nullptr : segs[0].table; // non-null: the table variants; null + segments: planes in the arguments
+    rc = k4 ? launch_yuv_resize(c, table.planes(), table.n_planes(), 1 << 30, ctx, false, nullptr) : launch_k1(c, table.planes(), table.n_planes(), ctx, false, nullptr);
+    if (rc != 1) return fail(CVGS_ERR_HIP, "fused kernel launch failed");
+    table.finish(true, &ctx);
+    return 1;
 }
 
 int execute_many(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream) {
-    if (n >= 2 && chains[0].read.kind == CVGS_READ_PIXEL) {
-        const int rc = pointwise_many(chains, n, stream);
-        if (rc == 1) return CVGS_OK;
-        if (rc < 0) return rc;
-    }
-    // try the fused launch: every chain a resize of pixels (K1) or of 4:2:0 surfaces (K4) into a planar tensor, all of one shape
-    bool fusable = n >= 2;
-    for (int i = 0; fusable && i < n; ++i) {
-        const cvgs_chain_desc& c = chains[i];
-        fusable = (c.read.kind == CVGS_READ_RESIZE_LINEAR || c.read.kind == CVGS_READ_NV12_RESIZE_LINEAR) &&
-                  !(c.flags & CVGS_CHAIN_FORCE_GENERIC) &&
-                  (c.write.kind == CVGS_WRITE_TENSOR_SPLIT || c.write.kind == CVGS_WRITE_TENSOR_T_SPLIT) && same_shape(chains[0], c) &&
-                  ((c.read.flags ^ chains[0].read.flags) & CVGS_READ_FLAG_TABLE_ON_DEVICE) == 0;
-    }
-    // whatever the one-by-one path would serve must not fail because the chains happen to share a shape.
-    //  * host descriptors under stream capture: the fused launch would stage a table (not capturable); one by one, chains of
-    //    <= 64 planes travel in kernel arguments and ARE capturable;
-    //  * a batch beyond the grid's y range;
-    //  * chains that are not independent (one writes where another writes or reads): the fused launch runs them concurrently,
-    //    n sequential cvgs_execute calls would not -- keep the sequential meaning.
-    // host-described K1 chains of u8 pixels with 3 / 4 channels, at most kManyInlineLarge planes in all: segments AND planes travel in the
-    // kernel arguments (cvgs_device.h: KernArgsManyInline) -- no table slot, nothing to recycle, capturable
-    bool inline_many = false;
-    if (fusable) {
-        const bool tables0 = (chains[0].read.flags & CVGS_READ_FLAG_TABLE_ON_DEVICE) != 0;
-        static const bool inline_ok = [] { const char* e = getenv("CVGS_MANY_INLINE"); return e ? e[0] != '0' : true; }();
-        const bool k1_u8 = chains[0].read.kind == CVGS_READ_RESIZE_LINEAR && CVGS_TYPE_CN(chains[0].read.src_type) >= 3 &&
-                           CVGS_TYPE_DEPTH(chains[0].read.src_type) == CVGS_DEPTH_8U;
-        const bool k4_il = chains[0].read.kind == CVGS_READ_NV12_RESIZE_LINEAR &&
-                           (chains[0].read.yuv_layout == CVGS_YUV_NV12 || chains[0].read.yuv_layout == CVGS_YUV_NV21 || chains[0].read.yuv_layout == CVGS_YUV_P010 ||
-                            is_yuv422(chains[0].read.yuv_layout) || is_yuv444(chains[0].read.yuv_layout)); // interleaved chroma / packed 4:2:2 / planar 4:4:4
-        if (!tables0 && inline_ok && (k1_u8 || k4_il)) {
-            size_t planes = 0;
-            for (int i = 0; i < n; ++i) planes += (size_t)(chains[i].read.batch > 0 ? chains[i].read.batch : 0);
-            inline_many = planes <= (size_t)cvgs::kManyInlineLarge;
-        }
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (!tables0 && !inline_many && hipStreamIsCapturing(stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) fusable = false;
-        for (int i = 0; fusable && i < n; ++i)
-            if (chains[i].read.batch < 1 || chains[i].read.batch > 65535) fusable = false;
-        if (fusable) {
-            const cvgs_chain_desc* ptrs[CVGS_MAX_CHAINS];
-            for (int i = 0; i < n; ++i) ptrs[i] = &chains[i];
-            fusable = chains_independent(ptrs, n);
-        }
-    }
-    if (fusable) {
-        const bool tables = (chains[0].read.flags & CVGS_READ_FLAG_TABLE_ON_DEVICE) != 0;
-        const bool k4 = chains[0].read.kind == CVGS_READ_NV12_RESIZE_LINEAR;
-        ManySeg segs[CVGS_MAX_CHAINS];
-        Upload up;
-        size_t total_planes = 0;
-        int max_batch = 0;
-        for (int i = 0; i < n; ++i) {
-            total_planes += (size_t)(chains[i].read.batch > 0 ? chains[i].read.batch : 0);
-            max_batch = std::max(max_batch, (int)chains[i].read.batch);
-        }
-        Lowered L0; // the shared read / program / write arguments come from chain 0
-        int rc = lower(&chains[0], false, L0);
-        if (rc) return rc;
-        if (L0.int_arith) fusable = false; // integer-typed arithmetic: the interpreted kernel, chain by chain
-        if (fusable) {
-            // would the fast kernel take this shape?  (dry run: nothing is enqueued, nothing uploaded)
-            ChainArgs probe = L0.args;
-            probe.read.table = (const PlaneParams*)(uintptr_t)16;
-            const ManySeg one{probe.read.table, probe.write.data, probe.read.batch, probe.read.used};
-            LaunchCtx pctx(stream);
-            pctx.segs = &one;
-            pctx.n_segs = 1;
-            if (k4) fusable = !tables && launch_yuv_resize(probe, nullptr, 0, 1 << 30, pctx, true, nullptr) == 1; // K4 checks its planes on the host
-            else fusable = launch_k1(probe, nullptr, 0, pctx, true, nullptr) == 1;
-        }
-        // host descriptors: the table goes into a slot of the stream's own ring, recycled through the launch's progress word (ManyPool) --
-        // or, when that ring has no room, into the event-tracked descriptor scratch
-        ManyStream* ms = nullptr;
-        ManySlot* mslot = nullptr;
-        std::unique_lock<std::mutex> ms_lock;
-        size_t ms_used = 0;
-        static thread_local std::vector<PlaneParams> inline_planes; // inline_many: every chain's planes, in chain order
-        inline_planes.clear();
-        if (fusable && !tables && !inline_many) {
-            const size_t bytes = total_planes * sizeof(PlaneParams) + 16 * (size_t)n;
-            static const bool progress_word = [] { const char* e = getenv("CVGS_MANY_PROGRESS_WORD"); return e ? e[0] != '0' : true; }();
-            if (progress_word && (ms = many_pool().get(stream, stream_device(stream))) != nullptr) {
-                ms_lock = std::unique_lock<std::mutex>(ms->mu);
-                mslot = many_pool().acquire(ms, bytes);
-                if (!mslot) { ms_lock.unlock(); ms = nullptr; }
-            }
-            if (!mslot) {
-                rc = up.begin(bytes, stream);
-                if (rc) return rc;
-            }
-        }
-        for (int i = 0; fusable && i < n; ++i) {
-            Lowered Li;
-            Lowered& L = i == 0 ? L0 : Li;
-            if (i > 0) rc = lower(&chains[i], false, L);
-            if (rc) return rc; // nothing enqueued yet
-            if (k4 && (L.args.read.used != L.args.read.batch ||
-                       !yuv_planes_eligible(L.args.read.yuv_layout, L.planes.data(), (int)L.planes.size(), L.args.read.dst_w, L.args.read.dst_h))) {
-                fusable = false; // e.g. a 2-pixel-wide crop: the one-by-one path sends that chain to the interpreted kernel
-                break;
-            }
-            segs[i].batch = L.args.read.batch;
-            segs[i].used = L.args.read.used;
-            segs[i].out = L.args.write.data;
-            if (tables) segs[i].table = L.args.read.table;
-            else if (inline_many) {
-                segs[i].table = (const PlaneParams*)(uintptr_t)inline_planes.size(); // the chain's first index into the argument block's planes
-                inline_planes.insert(inline_planes.end(), L.planes.data(), L.planes.data() + L.planes.size());
-            } else if (mslot) {
-                const size_t b = L.planes.size() * sizeof(PlaneParams);
-                std::memcpy((uint8_t*)mslot->host + ms_used, L.planes.data(), b);
-                segs[i].table = (const PlaneParams*)((uint8_t*)mslot->host_dev + ms_used);
-                ms_used += (b + 15) & ~(size_t)15;
-            } else segs[i].table = (const PlaneParams*)up.put(L.planes.data(), L.planes.size() * sizeof(PlaneParams));
-        }
-        if (fusable) {
-            if (!tables && !mslot && !inline_many) {
-                rc = up.flush();
-                if (rc) return rc;
-            }
-            if (inline_many && inline_planes.size() > (size_t)cvgs::kManyInlineLarge) return fail(CVGS_ERR_INVALID, "inline tick: more planes than counted");
-            ChainArgs c = L0.args;
-            c.read.batch = max_batch;
-            c.read.table = inline_many ? nullptr : segs[0].table; // non-null: the table variants; null + segments: planes in the arguments
-            LaunchCtx ctx(stream);
-            ctx.segs = segs;
-            ctx.n_segs = n;
-            ctx.stop_event = up.stop_event;
-            if (mslot) { // this launch is number next_seq of its stream: when it starts, number next_seq - 1 has finished
-                ctx.done_word = ms->done_dev;
-                ctx.done_value = ms->next_seq - 1;
-            }
-            rc = k4 ? launch_yuv_resize(c, inline_many ? inline_planes.data() : nullptr, inline_many ? (int)inline_planes.size() : 0, 1 << 30, ctx, false, nullptr)
-                    : launch_k1(c, inline_many ? inline_planes.data() : nullptr, inline_many ? (int)inline_planes.size() : 0, ctx, false, nullptr);
-            const bool reported = ctx.done_word_taken;
-            if (rc != 1) return fail(CVGS_ERR_HIP, "fused kernel launch failed");
-            if (mslot) {
-                if (reported) mslot->seq = ms->next_seq++;
-                else { // (a launch site that does not carry the word: make the slot safe the slow way -- not expected)
-                    (void)hipStreamSynchronize(stream);
-                    mslot->seq = 0;
-                }
-            }
-            up.done(true, ctx.stop_event_taken);
-            return CVGS_OK;
-        }
-        // not a fast-kernel shape after all (e.g. an integer-typed program): one by one below; nothing was enqueued
+    const TickPlan plan = plan_tick(chains, n, stream);
+    if (plan.family != TickFamily::none) {
+        const int rc = launch_tick(chains, n, plan, stream);
+        if (rc) return rc < 0 ? rc : CVGS_OK;
     }
     for (int i = 0; i < n; ++i) {
         Lowered L;
@@ -1981,12 +2011,25 @@ int cvgs_queue_create(cvgs_queue_t* out, int32_t device, int32_t depth, double i
     return CVGS_OK;
 }
 
+// The kinds no submission path of the queue has a kernel for, refused before anything else is looked at (handle, stream, device); 0: none of them
+static int queue_refuses_kinds(const cvgs_chain_desc* const* chains, int32_t n) {
+    for (int32_t i = 0; chains && i < n; ++i) {
+        if (chains[i] && is_area(chains[i]->read.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kAreaRefusal);
+        if (chains[i] && is_nv12_write(chains[i]->write.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kNv12WriteRefusal);
+    }
+    return 0;
+}
+// Is the lowered chain one the server takes?  (the rest is cvgs_execute's: the hybrid policy launches it, the plain submits refuse it)
+static bool queue_server_takes(const cvgs_chain_desc* chain, const Lowered& L) {
+    return !(L.uses_64f || L.int_arith || L.mirrors.n > 0 || is_warp(L.args.read.kind) || is_yuv422(L.args.read.yuv_layout) || is_yuv444(L.args.read.yuv_layout) ||
+             (chain->flags & CVGS_CHAIN_FORCE_GENERIC));
+}
+
 static int queue_submit_one(cvgs_queue_t h, const cvgs_chain_desc* chain, uint64_t* ticket) {
     Lowered L;
     int rc = lower(chain, false, L);
     if (rc) return rc;
-    if (L.uses_64f || L.int_arith || L.mirrors.n > 0 || is_warp(L.args.read.kind) || is_yuv422(L.args.read.yuv_layout) || is_yuv444(L.args.read.yuv_layout) || (chain->flags & CVGS_CHAIN_FORCE_GENERIC))
-        return fail(CVGS_ERR_UNSUPPORTED, "queue: not a chain the server takes");
+    if (!queue_server_takes(chain, L)) return fail(CVGS_ERR_UNSUPPORTED, "queue: not a chain the server takes");
     std::string err;
     rc = cvgs::queue_submit(h->q, L.args, L.planes.data(), (int)L.planes.size(), ticket, err);
     if (rc == 1) return fail(CVGS_ERR_UNSUPPORTED, err);
@@ -1995,8 +2038,7 @@ static int queue_submit_one(cvgs_queue_t h, const cvgs_chain_desc* chain, uint64
 }
 
 int cvgs_queue_submit(cvgs_queue_t h, const cvgs_chain_desc* chain, uint64_t* ticket) {
-    if (chain && is_area(chain->read.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kAreaRefusal);
-    if (chain && is_nv12_write(chain->write.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kNv12WriteRefusal);
+    if (int rc = queue_refuses_kinds(&chain, 1)) return rc;
     if (!h) return fail(CVGS_ERR_INVALID, "null queue");
     DeviceGuard guard;
     if (int rc = guard.enter(h->device)) return rc;
@@ -2004,10 +2046,7 @@ int cvgs_queue_submit(cvgs_queue_t h, const cvgs_chain_desc* chain, uint64_t* ti
 }
 
 int cvgs_queue_submit_many(cvgs_queue_t h, const cvgs_chain_desc* const* chains, int32_t n, uint64_t* last_ticket) {
-    for (int32_t i = 0; chains && i < n; ++i) {
-        if (chains[i] && is_area(chains[i]->read.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kAreaRefusal);
-        if (chains[i] && is_nv12_write(chains[i]->write.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kNv12WriteRefusal);
-    }
+    if (int rc = queue_refuses_kinds(chains, n)) return rc;
     if (!h || !chains || n < 1) return fail(CVGS_ERR_INVALID, "null queue / no chains");
     DeviceGuard guard;
     if (int rc = guard.enter(h->device)) return rc;
@@ -2019,8 +2058,7 @@ int cvgs_queue_submit_many(cvgs_queue_t h, const cvgs_chain_desc* const* chains,
 }
 
 int cvgs_queue_submit_on(cvgs_queue_t h, const cvgs_chain_desc* chain, cvgs_stream_t stream, uint32_t flags, uint64_t* ticket) {
-    if (chain && is_area(chain->read.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kAreaRefusal);
-    if (chain && is_nv12_write(chain->write.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kNv12WriteRefusal);
+    if (int rc = queue_refuses_kinds(&chain, 1)) return rc;
     if (!h) return fail(CVGS_ERR_INVALID, "null queue");
     if (flags & ~(uint32_t)(CVGS_QUEUE_SUBMIT_DEFER_WAIT | CVGS_QUEUE_SUBMIT_HYBRID | CVGS_QUEUE_SUBMIT_MIN_GROUP(0xff))) return fail(CVGS_ERR_INVALID, "queue: unknown submit flag bits");
     DeviceGuard guard;
@@ -2031,7 +2069,7 @@ int cvgs_queue_submit_on(cvgs_queue_t h, const cvgs_chain_desc* chain, cvgs_stre
     const bool hybrid = (flags & CVGS_QUEUE_SUBMIT_HYBRID) != 0;
     std::string err;
     rc = 1;
-    if (!(L.uses_64f || L.int_arith || L.mirrors.n > 0 || is_warp(L.args.read.kind) || is_yuv422(L.args.read.yuv_layout) || is_yuv444(L.args.read.yuv_layout) || (chain->flags & CVGS_CHAIN_FORCE_GENERIC))) {
+    if (queue_server_takes(chain, L)) {
         const cvgs::ChainArgs* ca = &L.args;
         const cvgs::PlaneParams* pp = L.planes.data();
         const int np = (int)L.planes.size();
@@ -2050,10 +2088,7 @@ int cvgs_queue_submit_on(cvgs_queue_t h, const cvgs_chain_desc* chain, cvgs_stre
 }
 
 int cvgs_queue_submit_many_on(cvgs_queue_t h, const cvgs_chain_desc* const* chains, int32_t n, cvgs_stream_t stream, uint32_t flags, uint64_t* last_ticket) {
-    for (int32_t i = 0; chains && i < n; ++i) {
-        if (chains[i] && is_area(chains[i]->read.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kAreaRefusal);
-        if (chains[i] && is_nv12_write(chains[i]->write.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kNv12WriteRefusal);
-    }
+    if (int rc = queue_refuses_kinds(chains, n)) return rc;
     if (!h || !chains || n < 1) return fail(CVGS_ERR_INVALID, "null queue / no chains");
     if (n > CVGS_QUEUE_MAX_GROUP) return fail(CVGS_ERR_INVALID, "queue: at most CVGS_QUEUE_MAX_GROUP chains behind one gate");
     if (flags & ~(uint32_t)(CVGS_QUEUE_SUBMIT_DEFER_WAIT | CVGS_QUEUE_SUBMIT_HYBRID | CVGS_QUEUE_SUBMIT_MIN_GROUP(0xff))) return fail(CVGS_ERR_INVALID, "queue: unknown submit flag bits");
@@ -2077,8 +2112,7 @@ int cvgs_queue_submit_many_on(cvgs_queue_t h, const cvgs_chain_desc* const* chai
     bool servable = true;
     for (int32_t i = 0; i < n; ++i) {
         if (int rc = lower(chains[i], false, L[(size_t)i])) return rc;
-        const Lowered& l = L[(size_t)i];
-        servable = servable && !(l.uses_64f || l.int_arith || l.mirrors.n > 0 || is_warp(l.args.read.kind) || is_yuv422(l.args.read.yuv_layout) || is_yuv444(l.args.read.yuv_layout) || (chains[i]->flags & CVGS_CHAIN_FORCE_GENERIC));
+        servable = servable && queue_server_takes(chains[i], L[(size_t)i]);
     }
     std::string err = "queue: not chains the server takes";
     int rc = 1, queued = 0;

@@ -60,18 +60,23 @@ def yuv_f32(rgb, color_range, primaries):
         return y, cb + f(128.0), cr + f(128.0)
 
 
+def block_mean_f32(c):
+    """The float chroma sample of every 2 x 2 block of a float32 plane [H, W]: top row, bottom row, then the quarter."""
+    assert c.dtype == np.float32
+    with np.errstate(all="ignore"):
+        m = ((c[0::2, 0::2] + c[0::2, 1::2]) + (c[1::2, 0::2] + c[1::2, 1::2])) * np.float32(0.25)
+    assert m.dtype == np.float32
+    return m
+
+
 def write_f32(rgb, color_range, primaries, layout=NV12):
     Y, U, V = yuv_f32(rgb, color_range, primaries)
     assert Y.dtype == np.float32 and U.dtype == np.float32 and Y.shape[0] % 2 == 0 and Y.shape[1] % 2 == 0
-    q = np.float32(0.25)
-    with np.errstate(all="ignore"):
-        ub = ((U[0::2, 0::2] + U[0::2, 1::2]) + (U[1::2, 0::2] + U[1::2, 1::2])) * q
-        vb = ((V[0::2, 0::2] + V[0::2, 1::2]) + (V[1::2, 0::2] + V[1::2, 1::2])) * q
-    assert ub.dtype == np.float32
-    return to_u8(Y), _interleave(to_u8(ub), to_u8(vb), layout)
+    return to_u8(Y), _interleave(to_u8(block_mean_f32(U)), to_u8(block_mean_f32(V)), layout)
 
 
-def write_f64(rgb, color_range, primaries, layout=NV12):
+def yuv_f64(rgb, color_range, primaries):
+    """The float64 model's values in front of the final rounding: (Y [H, W], U [H/2, W/2], V [H/2, W/2])."""
     rgb = np.asarray(rgb, np.float64)
     R, G, B = rgb[..., 0], rgb[..., 1], rgb[..., 2]
     kr, kg, kb, cu, cv = derived(primaries)
@@ -83,6 +88,11 @@ def write_f64(rgb, color_range, primaries, layout=NV12):
         Y, U, V = y, cb + 128.0, cr + 128.0
     ub = (U[0::2, 0::2] + U[0::2, 1::2] + U[1::2, 0::2] + U[1::2, 1::2]) / 4.0
     vb = (V[0::2, 0::2] + V[0::2, 1::2] + V[1::2, 0::2] + V[1::2, 1::2]) / 4.0
+    return Y, ub, vb
+
+
+def write_f64(rgb, color_range, primaries, layout=NV12):
+    Y, ub, vb = yuv_f64(rgb, color_range, primaries)
     return to_u8(Y), _interleave(to_u8(ub), to_u8(vb), layout)
 
 

@@ -30,21 +30,24 @@ def _torch():
 class Surface:
     """One target surface in a device buffer of its own: guard | luma rows | gap | chroma rows | guard, all SENTINEL before the launch."""
 
-    def __init__(self, device, w, h, gap=0):
+    def __init__(self, device, w, h, gap=0, step=None, lead=0):
+        """step: the row pitch (default width + PAD; any value >= width, odd ones included); lead: further bytes in front of the surface,
+        which shift its base address (the allocation itself is aligned)."""
         torch = _torch()
-        self.w, self.h, self.step = w, h, w + PAD
+        self.w, self.h, self.step = w, h, w + PAD if step is None else step
         self.uv_off = h * self.step + gap
         self.total = self.uv_off + (h // 2) * self.step
-        self.t = torch.full((GUARD + self.total + GUARD,), SENTINEL, dtype=torch.uint8, device=device)
-        self.mat = cvgs.GpuMat(h, w, cvgs.CV_8UC1, self.t.data_ptr() + GUARD, self.step, owner=self.t)
+        self.lead = GUARD + lead
+        self.t = torch.full((self.lead + self.total + GUARD,), SENTINEL, dtype=torch.uint8, device=device)
+        self.mat = cvgs.GpuMat(h, w, cvgs.CV_8UC1, self.t.data_ptr() + self.lead, self.step, owner=self.t)
         if gap:
             self.mat.uv_offset = self.uv_off
 
     def check(self, luma, chroma, what):
         got = self.t.cpu().numpy()
-        assert (got[:GUARD] == SENTINEL).all() and (got[GUARD + self.total:] == SENTINEL).all(), "%s: the guard band changed" % what
+        assert (got[:self.lead] == SENTINEL).all() and (got[self.lead + self.total:] == SENTINEL).all(), "%s: the guard band changed" % what
         want = M.surface_image(luma, chroma, self.step, self.uv_off, self.total, SENTINEL)
-        pay = got[GUARD:GUARD + self.total]
+        pay = got[self.lead:self.lead + self.total]
         bad = np.flatnonzero(pay != want)
         assert bad.size == 0, "%s: %d bytes differ, first at byte %d (row %d, column %d: got %d, want %d)" % (
             what, bad.size, bad[0], bad[0] // self.step, bad[0] % self.step, pay[bad[0]], want[bad[0]])
@@ -54,8 +57,9 @@ _frames = {}
 
 
 def frame(device, name):
-    """(host array, host GpuMat, device GpuMat) of a source; made once."""
-    if name not in _frames:
+    """(host array, host GpuMat, device GpuMat) of a source; made once per device.  device None: the host half alone (device GpuMat None)."""
+    key = (name, str(device))
+    if key not in _frames:
         rng = np.random.RandomState(21)
         if name == "NV12":
             host, cv_type, rows = M.random_surface(SW, SH, 3), cvgs.CV_8UC1, SH
@@ -65,11 +69,13 @@ def frame(device, name):
             host, cv_type, rows = rng.randint(0, 65536, (61, 97 * 3)).astype(np.uint16), cvgs.make_type(capi.DEPTH_16U, 3), 61
         else:  # 32FC3: a picture of the target's own size with values on both sides of 0..255
             host, cv_type, rows = (rng.rand(14, 34 * 3) * 300.0 - 20.0).astype(np.float32), F3, 14
-        t = _torch().from_numpy(host.view(np.uint8).reshape(host.shape[0], -1)).to(device)
         cols = SW if name == "NV12" else host.shape[1] // 3
-        _frames[name] = (host, cvgs.GpuMat(rows, cols, cv_type, host.ctypes.data, host.strides[0], owner=host),
-                         cvgs.GpuMat(rows, cols, cv_type, t.data_ptr(), host.strides[0], owner=t))
-    return _frames[name]
+        dm = None
+        if device is not None:
+            t = _torch().from_numpy(host.view(np.uint8).reshape(host.shape[0], -1)).to(device)
+            dm = cvgs.GpuMat(rows, cols, cv_type, t.data_ptr(), host.strides[0], owner=t)
+        _frames[key] = (host, cvgs.GpuMat(rows, cols, cv_type, host.ctypes.data, host.strides[0], owner=host), dm)
+    return _frames[key]
 
 
 def oracle_rgb(oracle, read, mid, dsize, batch):
@@ -80,20 +86,28 @@ def oracle_rgb(oracle, read, mid, dsize, batch):
     return ref.reshape(batch, h, w, 3)
 
 
-def run(device, oracle, what, make_read, mid, dsize, batch, out=(M.FULL, M.BT709, M.NV12), gap=0, kernel=None, both=True, rgb=None):
-    """The chain as dispatched and (both) with CHAIN_FORCE_GENERIC: each against the restatement.  make_read(mats_are_on_device) -> ReadIOp."""
+def run(device, oracle, what, make_read, mid, dsize, batch, out=(M.FULL, M.BT709, M.NV12), gap=0, kernel=None, both=True, rgb=None, make_outs=None):
+    """The chain as dispatched and (both) with CHAIN_FORCE_GENERIC: each against the restatement.  make_read(mats_are_on_device) -> ReadIOp.
+    make_outs() -> (target GpuMats, one per plane; check(want, label)): targets other than one Surface per plane, made anew for every run."""
     torch = _torch()
     rng, prim, layout = out
     if rgb is None:
         rgb = oracle_rgb(oracle, make_read(False), mid, dsize, batch)
     want = [M.write_f32(rgb[z], rng, prim, layout) for z in range(batch)]
     for flags in ((0, capi.CHAIN_FORCE_GENERIC) if both else (0,)):
-        outs = [Surface(device, dsize[0], dsize[1], gap) for _ in range(batch)]
-        ops = [make_read(True)] + list(mid) + [cvgs.write_nv12([o.mat for o in outs], rng, prim, layout)]
+        if make_outs is None:
+            outs = [Surface(device, dsize[0], dsize[1], gap) for _ in range(batch)]
+            mats, check_all = [o.mat for o in outs], None
+        else:
+            mats, check_all = make_outs()
+        ops = [make_read(True)] + list(mid) + [cvgs.write_nv12(mats, rng, prim, layout)]
         name = cvgs.kernel_name(*ops, flags=flags)
         assert name == ("nv12w_interp" if flags else (kernel or name)) and name.startswith("nv12w_"), name
         cvgs.executeOperations(torch.cuda.current_stream(), *ops, flags=flags)
         torch.cuda.synchronize()
+        if check_all is not None:
+            check_all(want, "%s, flags %d (%s)" % (what, flags, name))
+            continue
         for z, o in enumerate(outs):
             o.check(want[z][0], want[z][1], "%s, plane %d, flags %d (%s)" % (what, z, flags, name))
     return want

@@ -224,8 +224,8 @@ int launch_generic64(const ChainArgs& c, const Prog64Args& p64, const PlaneParam
 // picks the family from the layout.  1 launched / 0 not eligible / < 0 error.
 int launch_nv12(const ChainArgs& c, const PlaneParams* inline_planes, int n_inline, int min_width, LaunchCtx& ctx, bool dry_run, LaunchInfo* info,
                 uint32_t chain_flags = 0);
-// K4 at frame size, two output pixels per lane (k_nv12_x2.hip); 1 launched / 0 not eligible / < 0 error
-int launch_nv12_x2(const ChainArgs& c, const PlaneParams* planes, int n_planes, bool prog_swap, void* stream, bool dry_run);
+// K4 at frame size, two output pixels per lane (k_nv12_x2.hip); 1 launched / 0 not eligible / < 0 error.  *rows: the rows per wave of the form taken
+int launch_nv12_x2(const ChainArgs& c, const PlaneParams* planes, int n_planes, bool prog_swap, void* stream, bool dry_run, int* rows = nullptr);
 static constexpr int64_t kK4X2MinWaveRows = 4096; // output rows x 64-column tiles x surfaces from which launch_nv12 prefers it
 bool k4_planes_eligible(const PlaneParams* planes, int n, int dst_w, int dst_h);
 // Packed 4:2:2 surfaces (YUYV / UYVY) read back inside the bilinear resize (k_yuv422.hip): K4's targets and dispatch rules, any plane width.

@@ -8,6 +8,8 @@
 // pixel and source row: ONE unaligned 2-byte load brings both luma taps, ONE unaligned 4-byte load both chroma
 // pairs (4 loads per pixel instead of 12 byte loads); windows are clamped into the row.  Planar stores are
 // full-wave 256-byte rows, non-temporal.
+#include <cstdio>
+
 #include "k_yuv_family.hpp"
 
 namespace cvgs {
@@ -375,8 +377,17 @@ struct K4FamilyBase : YuvFamDefaults {
         const char* x2_env = getenv("CVGS_K4_X2"); // tuning / test hook: 0 = never, 1 = whenever eligible
         const int64_t wave_rows = (int64_t)r.batch * r.dst_h * ((r.dst_w + 63) / 64);
         if (!(x2_env ? x2_env[0] == '1' : wave_rows >= kK4X2MinWaveRows)) return 0;
-        const int rc = launch_nv12_x2(c, planes, n, prog_swap, ctx.stream, dry_run);
-        if (rc != 0 && info) info->kernel = prog_swap ? "k4_nv12_x2_swap_mul_sub_div" : "k4_nv12_x2_mul_sub_div";
+        int rows = 0;
+        const int rc = launch_nv12_x2(c, planes, n, prog_swap, ctx.stream, dry_run, &rows);
+        if (rc != 0 && info) {
+            info->kernel = prog_swap ? "k4_nv12_x2_swap_mul_sub_div" : "k4_nv12_x2_mul_sub_div";
+            if (x2_env) { // under the hook, and only then, the name says which form was taken: "@r1" / "@r2" (tests/test_k4_x2_cases.py), as k_k1.hip's does:
+                // a per-thread buffer, valid until this thread's next call that asks for a name; cvgs_kernel_name copies it out before it returns
+                static thread_local char hooked[96];
+                snprintf(hooked, sizeof(hooked), "%s@r%d", info->kernel, rows);
+                info->kernel = hooked;
+            }
+        }
         return rc;
     }
 };

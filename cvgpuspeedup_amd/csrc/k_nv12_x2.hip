@@ -22,7 +22,8 @@
 // diet; the arithmetic now hides under the load phase).  The skeleton itself is a launch floor + 26 MB that every wave reads, then
 // writes, in the same phase: a single frame-size launch has no second launch to overlap with (ticks of several surfaces do: 5.2 us per frame).
 // Stretch geometry only (every surface covers its whole target), NV12 / NV21 8-bit, three channels, the two compile-time
-// programs; everything else stays on k4_nv12_resize.  Bit-identical to it and to the oracle (tests/test_gpu_k4_x2.py).
+// programs; everything else stays on k4_nv12_resize.  Bit-identical to it and to the oracle (tests/test_gpu_k4_x2.py: the one-row
+// form; tests/test_zz_gpu_k4_x2_rows.py: the pipelined one).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -285,8 +286,9 @@ __global__ __launch_bounds__(64 * WAVES) void k4_nv12_x2(N2_PRELOADED_PARAMS, co
 }
 
 // Host side: 1 launched / 0 not eligible / < 0 error (as launch_nv12).  `c.prog` holds the chain's program with its trailing
-// stages as launch_nv12 prepared them (fast_div set up); prog_swap says which compile-time program it is.
-int launch_nv12_x2(const ChainArgs& c, const PlaneParams* planes, int n_planes, bool prog_swap, void* stream, bool dry_run) {
+// stages as launch_nv12 prepared them (fast_div set up); prog_swap says which compile-time program it is.  *rows (if asked for): the
+// rows per wave of the form taken, 1 or kN2Rows -- a dry run reports it too.
+int launch_nv12_x2(const ChainArgs& c, const PlaneParams* planes, int n_planes, bool prog_swap, void* stream, bool dry_run, int* rows) {
     const ReadArgs& r = c.read;
     const WriteArgs& w = c.write;
     if (r.kind != CVGS_READ_NV12_RESIZE_LINEAR || (r.yuv_layout != CVGS_YUV_NV12 && r.yuv_layout != CVGS_YUV_NV21) || r.out_cn != 3) return 0;
@@ -298,6 +300,13 @@ int launch_nv12_x2(const ChainArgs& c, const PlaneParams* planes, int n_planes, 
         if (i < n_planes && (p.w < 4 || p.x1 != 0 || p.y1 != 0 || p.x2 != r.dst_w - 1 || p.y2 != r.dst_h - 1)) return 0;
         a.plane[i] = N2Plane{p.data, p.w, p.h, p.step, p.uv_off, p.fx, p.fy};
     }
+    // rows per wave: 1 (small / odd-width targets: maximum parallelism, the last lane may store ONE pixel; tests/test_gpu_k4_x2.py runs this
+    // form) or kN2Rows, walked with the next row's loads in flight (even widths, tensors below 4 GB: the stores go through one buffer
+    // descriptor; tests/test_zz_gpu_k4_x2_rows.py runs this one, on the cases of tests/k4_x2_cases.py)
+    const int64_t total_bytes = ((int64_t)(r.batch - 1) * w.img_stride + 2 * w.ch_stride + (int64_t)r.dst_h * w.width) * 4;
+    const bool pipe = (r.dst_w & 1) == 0 && total_bytes > 0 && total_bytes < ((int64_t)1 << 32) - 65536 &&
+                      (int64_t)r.batch * r.dst_h * ((r.dst_w + 127) / 128) >= 4096;
+    if (rows) *rows = pipe ? kN2Rows : 1;
     if (dry_run) return 1;
     a.out = (float*)w.data;
     a.img_stride = w.img_stride;
@@ -309,11 +318,6 @@ int launch_nv12_x2(const ChainArgs& c, const PlaneParams* planes, int n_planes, 
     a.yuv_primaries = r.yuv_primaries;
     a.yuv_vu = r.yuv_layout == CVGS_YUV_NV21;
     a.prog = c.prog;
-    // rows per wave: 1 (small / odd-width targets: maximum parallelism, the last lane may store ONE pixel) or kN2Rows, walked with the
-    // next row's loads in flight (even widths, tensors below 4 GB: the stores go through one buffer descriptor)
-    const int64_t total_bytes = ((int64_t)(r.batch - 1) * w.img_stride + 2 * w.ch_stride + (int64_t)r.dst_h * w.width) * 4;
-    const bool pipe = (r.dst_w & 1) == 0 && total_bytes > 0 && total_bytes < ((int64_t)1 << 32) - 65536 &&
-                      (int64_t)r.batch * r.dst_h * ((r.dst_w + 127) / 128) >= 4096;
     a.out_bytes = pipe ? (uint32_t)total_bytes : 0u;
     const int rpw = pipe ? kN2Rows : 1, waves = pipe ? kN2PipeWaves : kN2Waves;
     const unsigned col_tiles = (unsigned)((r.dst_w + 127) / 128), row_groups = (unsigned)((r.dst_h + waves * rpw - 1) / (waves * rpw));

@@ -1,8 +1,11 @@
 """K4 at frame size, two output pixels per lane (csrc/k_nv12_x2.hip): crops of NV12 / NV21 decoder surfaces stretched into a
 planar fp32 tensor behind the two compile-time programs -- BASELINE cfg #3's chain (reference tests/resize/test_fused_resize.cu:141-147
 + the K1 tail).  Bit-exact vs the oracle and identical to the one-pixel kernel (CVGS_CHAIN_NO_THREAD_FUSION) and to the interpreted
-kernel.  CVGS_K4_X2=1 makes launch_nv12 pick the kernel whenever the chain is eligible (small, ragged and odd targets included);
-the size rule itself is checked on cfg #3's own shape."""
+kernel.  CVGS_K4_X2=1 makes launch_nv12 pick the kernel whenever the chain is eligible, and the name then says which of its two forms
+launch_nv12_x2 took: every forced shape here is small or odd and takes the ONE-ROW form ("@r1": one row per wave, plain stores, an odd
+target's last lane stores one pixel).  The pipelined form ("@r2": two rows per wave, stores through one buffer descriptor) runs here on
+cfg #3's own shape only, where the size rules are checked without the hook; tests/test_zz_gpu_k4_x2_rows.py (cases: tests/k4_x2_cases.py)
+runs it on small, odd and batched targets."""
 import os
 
 import numpy as np
@@ -72,7 +75,7 @@ SHAPES = [((640, 360), (133, 75)), ((322, 198), (640, 400)), ((640, 360), (213, 
 def test_x2_matches_the_oracle(forced, oracle, shape, layout, range_, prim, swap):
     (w, h), dst = shape
     surf = H.random_u8((h + h // 2, w), 8000 + w + h)
-    _run(oracle, surf, w, h, [(0, 0, w, h)], dst, range_, prim, layout, swap, "k4_nv12_x2_swap_mul_sub_div" if swap else "k4_nv12_x2_mul_sub_div")
+    _run(oracle, surf, w, h, [(0, 0, w, h)], dst, range_, prim, layout, swap, "k4_nv12_x2_swap_mul_sub_div@r1" if swap else "k4_nv12_x2_mul_sub_div@r1")
 
 
 def test_x2_crops_of_a_surface_as_one_batch(forced, oracle):
@@ -80,7 +83,7 @@ def test_x2_crops_of_a_surface_as_one_batch(forced, oracle):
     w, h = 1280, 720
     surf = H.random_u8((h + h // 2, w), 8100)
     crops = [tuple(v & ~1 for v in c) for c in H.random_crops(6, w, h, seed=81, wmin=9, wmax=600, hmin=9, hmax=400)] + [(w - 4, h - 2, 4, 2), (0, 0, w, h)]
-    _run(oracle, surf, w, h, crops, (96, 54), capi.YUV_LIMITED, capi.BT709, capi.YUV_NV12, True, "k4_nv12_x2_swap_mul_sub_div")
+    _run(oracle, surf, w, h, crops, (96, 54), capi.YUV_LIMITED, capi.BT709, capi.YUV_NV12, True, "k4_nv12_x2_swap_mul_sub_div@r1")
 
 
 def test_x2_extreme_samples(forced, oracle):
@@ -92,7 +95,7 @@ def test_x2_extreme_samples(forced, oracle):
     surf[h:, ::4] = 255
     surf[h + 1::2, 1::4] = 255
     for dst in ((128, 64), (512, 256), (100, 33)):
-        _run(oracle, surf, w, h, [(0, 0, w, h)], dst, capi.YUV_FULL, capi.BT601, capi.YUV_NV12, True, "k4_nv12_x2_swap_mul_sub_div")
+        _run(oracle, surf, w, h, [(0, 0, w, h)], dst, capi.YUV_FULL, capi.BT601, capi.YUV_NV12, True, "k4_nv12_x2_swap_mul_sub_div@r1")
 
 
 def test_x2_is_the_default_at_cfg3_and_leaves_the_rest(oracle):

@@ -53,6 +53,7 @@ def cast_aux(t):
 # read kinds
 READ_PIXEL, READ_RESIZE_LINEAR, READ_NV12, READ_NV12_RESIZE_LINEAR, READ_WARP_AFFINE, READ_WARP_PERSPECTIVE = range(6)
 READ_RESIZE_AREA = 6  # INTER_AREA (box filter): the fields and the plane table of READ_RESIZE_LINEAR, kernels of its own
+READ_NV12_RESIZE_AREA = 8  # INTER_AREA of NV12 / NV21 / P010 decoder surfaces: the fields and the plane table of READ_NV12_RESIZE_LINEAR (7: reserved)
 # aspect ratio (same values as cvGS::AspectRatio)
 PRESERVE_AR, IGNORE_AR, PRESERVE_AR_RN_EVEN, PRESERVE_AR_LEFT = 0, 1, 2, 3
 YUV_FULL, YUV_LIMITED = 0, 1

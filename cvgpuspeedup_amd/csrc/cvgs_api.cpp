@@ -69,16 +69,25 @@ int cast_depth(int aux) {
 
 bool is_resize(int kind) { return kind == CVGS_READ_RESIZE_LINEAR || kind == CVGS_READ_NV12_RESIZE_LINEAR; }
 constexpr int kMaxDim = CVGS_MAX_DIM; // widest / tallest plane the 32-bit index arithmetic of the kernels is specified for
-bool is_nv12(int kind) { return kind == CVGS_READ_NV12 || kind == CVGS_READ_NV12_RESIZE_LINEAR; }
+bool is_nv12(int kind) { return kind == CVGS_READ_NV12 || kind == CVGS_READ_NV12_RESIZE_LINEAR || kind == CVGS_READ_NV12_RESIZE_AREA; }
 bool is_yuv422(int layout) { return layout == CVGS_YUV_YUYV || layout == CVGS_YUV_UYVY; } // packed 4:2:2: one plane of 4-byte pixel pairs
 bool is_yuv444(int layout) { return layout == CVGS_YUV_I444; } // planar 4:4:4: three full-resolution planes, uv_offset apart
 bool is_warp(int kind) { return kind == CVGS_READ_WARP_AFFINE || kind == CVGS_READ_WARP_PERSPECTIVE; }
 // INTER_AREA: the bilinear resize's fields, geometry and plane table, kernels of its own (k_area.hip).  NOT in is_resize(): every site that
 // asks is_resize() means "a bilinear kernel may serve this"; the sites that mean "planes carry plane_geometry" ask has_geometry().
 bool is_area(int kind) { return kind == CVGS_READ_RESIZE_AREA; }
-bool has_geometry(int kind) { return is_resize(kind) || is_area(kind); }
+// INTER_AREA of 4:2:0 decoder surfaces: the bilinear NV12 resize's fields, geometry and plane table, kernels of its own (k_yuv_area.hip).
+// In is_nv12() (a decoder surface is validated and addressed as one), NOT in is_resize() and NOT in is_area() (whose sites speak of pixels).
+bool is_yuv_area(int kind) { return kind == CVGS_READ_NV12_RESIZE_AREA; }
+bool any_area(int kind) { return is_area(kind) || is_yuv_area(kind); }
+bool has_geometry(int kind) { return is_resize(kind) || any_area(kind); }
+const char* yuv_layout_name(int layout) {
+    static const char* const names[] = {"NV12", "NV21", "I420", "YV12", "P010", "YUYV", "UYVY", "I444"};
+    return layout >= CVGS_YUV_NV12 && layout <= CVGS_YUV_I444 ? names[layout] : "?";
+}
 // The submission paths that have no AREA kernel refuse the kind before they touch anything else (handle, stream, device).
 const char* const kAreaRefusal = ": INTER_AREA reads (CVGS_READ_RESIZE_AREA) are served by cvgs_execute / cvgs_execute_many only";
+const char* const kYuvAreaRefusal = ": INTER_AREA reads of decoder surfaces (CVGS_READ_NV12_RESIZE_AREA) are served by cvgs_execute / cvgs_execute_many only";
 // NV12 / NV21 encoder surfaces as the write stage (k_nv12_write.hip): a launcher of its own, in front of every other one (dispatch), and the
 // same rule for the submission paths that have no kernel for it.
 bool is_nv12_write(int kind) { return kind == CVGS_WRITE_NV12; }
@@ -192,11 +201,12 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
         return fail(CVGS_ERR_INVALID, "unknown chain flags");
     const cvgs_read_desc& rd = ch->read;
     const cvgs_write_desc& wr = ch->write;
-    if (rd.kind < CVGS_READ_PIXEL || rd.kind > CVGS_READ_RESIZE_AREA) return fail(CVGS_ERR_INVALID, "bad read kind");
+    if (rd.kind < CVGS_READ_PIXEL || rd.kind > CVGS_READ_NV12_RESIZE_AREA || rd.kind == 7 /* reserved */) return fail(CVGS_ERR_INVALID, "bad read kind");
     if (is_nv12_write(wr.kind)) { // what has no kernel is said first, before any field of the chain is judged
         if (circular) return fail(CVGS_ERR_UNSUPPORTED, std::string("CircularTensor::update") + kNv12WriteRefusal);
         if (is_warp(rd.kind)) return fail(CVGS_ERR_UNSUPPORTED, "NV12 surface writes behind warp reads (no kernel: warp into an image, then convert it)");
         if (is_area(rd.kind)) return fail(CVGS_ERR_UNSUPPORTED, "NV12 surface writes behind INTER_AREA reads (no kernel: CVGS_READ_RESIZE_AREA writes pixels and tensors)");
+        if (is_yuv_area(rd.kind)) return fail(CVGS_ERR_UNSUPPORTED, "NV12 surface writes behind INTER_AREA reads of decoder surfaces (no kernel: CVGS_READ_NV12_RESIZE_AREA writes pixels and tensors)");
         if (wr.n_mirrors > 0) return fail(CVGS_ERR_UNSUPPORTED, "mirrors on NV12 surface writes (mirrors exist for tensor write kinds)");
     }
     if (rd.batch < 1 || rd.batch > 65535) return fail(CVGS_ERR_INVALID, "batch must be in [1, 65535]");
@@ -210,6 +220,8 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
         if (rd.yuv_layout < CVGS_YUV_NV12 || rd.yuv_layout > CVGS_YUV_I444) return fail(CVGS_ERR_INVALID, "bad yuv_layout");
         if (rd.yuv_range < CVGS_YUV_FULL || rd.yuv_range > CVGS_YUV_LIMITED) return fail(CVGS_ERR_INVALID, "bad yuv_range");
         if (rd.yuv_primaries < CVGS_BT601 || rd.yuv_primaries > CVGS_BT2020) return fail(CVGS_ERR_INVALID, "bad yuv_primaries");
+        if (is_yuv_area(rd.kind) && rd.yuv_layout != CVGS_YUV_NV12 && rd.yuv_layout != CVGS_YUV_NV21 && rd.yuv_layout != CVGS_YUV_P010)
+            return fail(CVGS_ERR_UNSUPPORTED, std::string("INTER_AREA reads of ") + yuv_layout_name(rd.yuv_layout) + " surfaces (CVGS_READ_NV12_RESIZE_AREA serves NV12, NV21 and P010)");
         if (rd.yuv_layout == CVGS_YUV_P010) {
             if (rd.src_type != CVGS_MAKETYPE(CVGS_DEPTH_16U, 1)) return fail(CVGS_ERR_INVALID, "P010 reads need a CV_16UC1 source");
         } else if (is_yuv422(rd.yuv_layout)) {
@@ -310,7 +322,8 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
             if (im.step < im.width * esz) return fail(CVGS_ERR_INVALID, "source step smaller than a row");
             const bool p422 = is_nv12(rd.kind) && is_yuv422(rd.yuv_layout);
             const bool p444 = is_nv12(rd.kind) && is_yuv444(rd.yuv_layout);
-            if (is_nv12(rd.kind) && !p422 && !p444 && ((im.width & 1) || (im.height & 1)))
+            // (the AREA kind gives the last chroma sample of an odd view its half weight: include/cvgs_hip.h)
+            if (is_nv12(rd.kind) && !is_yuv_area(rd.kind) && !p422 && !p444 && ((im.width & 1) || (im.height & 1)))
                 return fail(CVGS_ERR_INVALID, "NV12 planes need even dimensions");
             PlaneParams& P = L.planes[(size_t)z];
             P.data = (const uint8_t*)im.data;
@@ -424,6 +437,8 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
     if (sdepth == CVGS_DEPTH_64F || L.final_depth == CVGS_DEPTH_64F) L.uses_64f = true;
     if (is_area(rd.kind) && L.uses_64f) return fail(CVGS_ERR_UNSUPPORTED, "INTER_AREA chains with CV_64F values (no kernel: the interpreted AREA kernel computes in fp32)");
     if (is_area(rd.kind) && wr.n_mirrors > 0) return fail(CVGS_ERR_UNSUPPORTED, "mirrors on INTER_AREA chains");
+    if (is_yuv_area(rd.kind) && L.uses_64f) return fail(CVGS_ERR_UNSUPPORTED, "INTER_AREA reads of decoder surfaces in chains with CV_64F values (no kernel: the NV12 AREA kernels compute in fp32)");
+    if (is_yuv_area(rd.kind) && wr.n_mirrors > 0) return fail(CVGS_ERR_UNSUPPORTED, "mirrors on INTER_AREA reads of decoder surfaces");
     if (is_nv12_write(wr.kind) && L.uses_64f) return fail(CVGS_ERR_UNSUPPORTED, "NV12 surface writes of chains with CV_64F values (no kernel: the conversion is specified in fp32)");
 
     // ---- write stage ----
@@ -1012,7 +1027,7 @@ int dispatch(const cvgs_chain_desc* ch, Lowered& L, hipStream_t stream, bool dry
     // 65 .. CVGS_KERNARG_PLANES_MAX planes of a chain K1 serves with a planar tensor target: the descriptors still travel in
     // the kernel arguments (a 16 KB block) -- no staging copy, capturable into a HIP graph
     bool big_inline = false;
-    const bool area = is_area(L.args.read.kind);
+    const bool area = any_area(L.args.read.kind);
     const bool nv12w = is_nv12_write(L.args.write.kind);
     if (!warp && !area && !nv12w && !L.uses_64f && !L.int_arith && !L.args.read.table && !(ch->flags & CVGS_CHAIN_FORCE_GENERIC) &&
         (int)L.planes.size() > CVGS_KERNARG_PLANES && (int)L.planes.size() <= kKernargPlanesBig)
@@ -1079,7 +1094,9 @@ int dispatch(const cvgs_chain_desc* ch, Lowered& L, hipStream_t stream, bool dry
     }
     if (area) { // its own launcher, and nothing below: every kernel further down would read the planes as bilinear taps
         if (has_mirrors || L.uses_64f) return fail(CVGS_ERR_UNSUPPORTED, "mirrors / CV_64F values on INTER_AREA chains");
-        if (launch_area(L.args, inline_planes, n_inline, ch->flags, stream, dry_run, info)) return fail(CVGS_ERR_HIP, "area kernel launch failed");
+        if (is_yuv_area(L.args.read.kind) ? launch_yuv_area(L.args, inline_planes, n_inline, ch->flags, stream, dry_run, info)
+                                          : launch_area(L.args, inline_planes, n_inline, ch->flags, stream, dry_run, info))
+            return fail(CVGS_ERR_HIP, "area kernel launch failed");
         up.done(true);
         return CVGS_OK;
     }
@@ -1196,8 +1213,10 @@ static void source_range(const cvgs_chain_desc& c, const cvgs_image2d& im, size_
         const size_t chroma_rows = (rows + 1) / 2;
         const uint8_t* cbase = im.uv_offset ? lo + (size_t)im.uv_offset : lo + (size_t)im.step * rows;
         const bool planar_chroma = c.read.yuv_layout == CVGS_YUV_I420 || c.read.yuv_layout == CVGS_YUV_YV12;
+        // interleaved chroma: whole (U, V) pairs -- an odd view (the AREA kind takes them) reads the pair of its last column whole
+        const size_t last_chroma_row = 2 * (((size_t)(im.width > 0 ? im.width : 1) + 1) / 2) * px_bytes;
         const uint8_t* chi = planar_chroma ? cbase + (size_t)im.step * chroma_rows // (two half-width planes: the upper bound)
-                                           : cbase + (size_t)im.step * (chroma_rows - 1) + last_row;
+                                           : cbase + (size_t)im.step * (chroma_rows - 1) + last_chroma_row;
         if (chi > hi) hi = chi;
     }
     *out = ByteRange{lo, hi};
@@ -1690,6 +1709,7 @@ int cvgs_plane_tables_from_boxes(const cvgs_box_table_desc* descs, int32_t n, cv
         if (d.struct_size != sizeof(cvgs_box_table_desc)) return fail(CVGS_ERR_INVALID, "cvgs_box_table_desc size mismatch (ABI)");
         if (d.flags) return fail(CVGS_ERR_INVALID, "plane_tables_from_boxes: flags must be 0");
         if (is_area(d.read_kind)) return fail(CVGS_ERR_UNSUPPORTED, "plane_tables_from_boxes: an INTER_AREA chain takes the table of the same chain spelled CVGS_READ_RESIZE_LINEAR (one layout: build it with that kind)");
+        if (is_yuv_area(d.read_kind)) return fail(CVGS_ERR_UNSUPPORTED, "plane_tables_from_boxes: an INTER_AREA chain over a decoder surface takes the table of the same chain spelled CVGS_READ_NV12_RESIZE_LINEAR (one layout: build it with that kind)");
         if (d.read_kind < CVGS_READ_PIXEL || d.read_kind > CVGS_READ_WARP_PERSPECTIVE) return fail(CVGS_ERR_INVALID, "bad read kind");
         if (is_warp(d.read_kind)) return fail(CVGS_ERR_UNSUPPORTED, "plane_tables_from_boxes: warp reads (WARP_AFFINE / WARP_PERSPECTIVE) take host descriptors");
         if (!is_resize(d.read_kind))
@@ -1916,6 +1936,7 @@ int cvgs_circular_create_ex(cvgs_circular_t* out, int32_t width, int32_t height,
 
 int cvgs_circular_update(cvgs_circular_t ct, const cvgs_chain_desc* chain, cvgs_stream_t stream) {
     if (chain && is_area(chain->read.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("CircularTensor::update") + kAreaRefusal);
+    if (chain && is_yuv_area(chain->read.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("CircularTensor::update") + kYuvAreaRefusal);
     if (chain && is_nv12_write(chain->write.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("CircularTensor::update") + kNv12WriteRefusal);
     if (!ct || !chain) return fail(CVGS_ERR_INVALID, "null argument");
     if (!ct->capturable) {
@@ -2015,6 +2036,7 @@ int cvgs_queue_create(cvgs_queue_t* out, int32_t device, int32_t depth, double i
 static int queue_refuses_kinds(const cvgs_chain_desc* const* chains, int32_t n) {
     for (int32_t i = 0; chains && i < n; ++i) {
         if (chains[i] && is_area(chains[i]->read.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kAreaRefusal);
+        if (chains[i] && is_yuv_area(chains[i]->read.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kYuvAreaRefusal);
         if (chains[i] && is_nv12_write(chains[i]->write.kind)) return fail(CVGS_ERR_UNSUPPORTED, std::string("queue") + kNv12WriteRefusal);
     }
     return 0;

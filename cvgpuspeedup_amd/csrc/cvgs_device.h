@@ -259,6 +259,11 @@ int launch_warp(const ChainArgs& c, const WarpPlane* planes, int n, const WarpPl
 // else c.read.table).  The fast kernels (u8 C3/C4 -> static program -> planar fp32 / fp16 / bf16 tensor) or the interpreted one; 0 or a HIP error code
 int launch_area(const ChainArgs& c, const PlaneParams* inline_planes, int n_inline, uint32_t chain_flags, void* stream, bool dry_run, LaunchInfo* info);
 
+// INTER_AREA resize of 4:2:0 decoder surfaces (k_yuv_area.hip): CVGS_READ_NV12_RESIZE_AREA chains over NV12 / NV21 / P010 views, planes as for
+// the bilinear NV12 resize.  The fast kernels (8-bit NV12 / NV21 -> static program -> planar fp32 / fp16 / bf16 tensor) or the interpreted one;
+// 0 or a HIP error code
+int launch_yuv_area(const ChainArgs& c, const PlaneParams* inline_planes, int n_inline, uint32_t chain_flags, void* stream, bool dry_run, LaunchInfo* info);
+
 // NV12 / NV21 encoder surfaces (k_nv12_write.hip): CVGS_WRITE_NV12 chains behind a per-pixel, bilinear or NV12 read, planes as for the
 // bilinear resize, targets in c.dst_inline / c.write.table (DstPlane::pad = the chroma offset).  The fast kernel (NV12 / NV21 surface ->
 // resize -> surface, empty program) or the interpreted one; 0 or a HIP error code

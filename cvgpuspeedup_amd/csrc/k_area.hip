@@ -3,54 +3,16 @@
 // by the share of it the output pixel covers, where the bilinear kernels read 2 x 2 of them.  The planes are the bilinear resize's
 // PlaneParams (fx, fy, window), inline in the kernel arguments or in a device table.
 // The arithmetic is the contract written down in include/cvgs_hip.h (strict fp32, every operation rounded once, in the written order);
-// BOTH kernels below run the same text for it (area_axis / area_w, the same loop nest), so the fast kernel is bit-identical to the
+// BOTH kernels below run the same text for it (area_axis / area_w of k_area_axis.hpp, the same loop nest), so the fast kernel is bit-identical to the
 // interpreted one.  One lane = one output pixel; the tap loops are dynamic loops over the footprint and every weight is recomputed from
 // (a, b, index) inside them: no per-lane arrays, nothing in scratch or LDS.  Adjacent lanes own adjacent footprints, so a wave's loads of
 // one source row form one contiguous span.
 #include <type_traits>
 
+#include "k_area_axis.hpp"
 #include "k_taps.hpp"
 
 namespace cvgs {
-
-// One axis of one output pixel: the taps are source indices i0 .. i0 + cnt - 1 (clamped to n - 1), tap j weighs area_w(A, j), W is their sum.
-struct AreaAxis {
-    float a, b; // shrinking: the footprint [a, b) in source pixels; not shrinking: a = the bilinear source position, b unused
-    float W;
-    int i0, cnt;
-    bool shrink;
-};
-
-__device__ __forceinline__ float area_w(const AreaAxis& A, int j) {
-    if (A.shrink) {
-        if (A.b <= A.a) return 1.0f; // (a footprint that rounding emptied: the single tap i0)
-        const int i = A.i0 + j;
-        return fminf((float)(i + 1), A.b) - fmaxf((float)i, A.a);
-    }
-    return j == 0 ? (float)(A.i0 + 1) - A.a : A.a - (float)A.i0; // the bilinear pair
-}
-
-// t = output coordinate inside the window, f = source step per output pixel, n = source extent
-__device__ __forceinline__ AreaAxis area_axis(int t, float f, int n) {
-    AreaAxis A;
-    A.shrink = f > 1.0f;
-    A.a = (float)t * f;
-    if (A.shrink) {
-        A.b = fminf((float)(t + 1) * f, (float)n);
-        A.i0 = min((int)floorf(A.a), n - 1);
-        const int i1 = max(min((int)ceilf(A.b), n), A.i0 + 1);
-        A.cnt = i1 - A.i0;
-        float W = 0.0f;
-        for (int j = 0; j < A.cnt; ++j) W = W + area_w(A, j);
-        A.W = W;
-    } else {
-        A.b = 0.0f;
-        A.i0 = (int)floorf(A.a);
-        A.cnt = 2;
-        A.W = 1.0f; // by definition, not summed
-    }
-    return A;
-}
 
 // ---- the interpreted kernel: every source type the bilinear resize reads (CV_64F excepted), interpreted program, generic write stage ----
 template <int NPL>

@@ -41,6 +41,7 @@ COLOR_RGBA2GRAY = 11
 SUPPORTED_COLOR_CONVERSIONS = (0, 1, 2, 3, 4, 5, 6, 7, 10, 11)
 SUPPORTED_INTERPOLATIONS = (INTER_LINEAR, INTER_AREA)
 _RESIZE_KIND = {INTER_LINEAR: capi.READ_RESIZE_LINEAR, INTER_AREA: capi.READ_RESIZE_AREA}
+_NV12_RESIZE_KIND = {INTER_LINEAR: capi.READ_NV12_RESIZE_LINEAR, INTER_AREA: capi.READ_NV12_RESIZE_AREA}
 
 PRESERVE_AR, IGNORE_AR, PRESERVE_AR_RN_EVEN, PRESERVE_AR_LEFT = 0, 1, 2, 3  # cvGS::AspectRatio
 NewestFirst, OldestFirst = capi.NEWEST_FIRST, capi.OLDEST_FIRST                # fk::CircularTensorOrder
@@ -103,6 +104,19 @@ class GpuMat:
         if (x | y | w | h) & 1:
             raise ValueError("NV12 crops need even x, y, width and height")
         if x < 0 or y < 0 or x + w > self.cols or y + h > self.rows:
+            raise ValueError("ROI outside the matrix")
+        parent_uv = getattr(self, "uv_offset", 0) or self.rows * self.step
+        m = GpuMat(h, w, self.cv_type, self.data + y * self.step + x * elem_size(self.cv_type), self.step, owner=self.owner)
+        m.uv_offset = parent_uv + (y // 2 - y) * self.step
+        return m
+
+    def nv12_area_roi(self, x, y, w, h):
+        """nv12_roi for the INTER_AREA read (read_nv12(..., interp=INTER_AREA)): x and y must be even, width and height may be odd -- the
+        last chroma sample of an odd view then lies under one luma column / row only."""
+        x, y, w, h = int(x), int(y), int(w), int(h)
+        if (x | y) & 1:
+            raise ValueError("NV12 crops need even x and y")
+        if x < 0 or y < 0 or w < 1 or h < 1 or x + w > self.cols or y + h > self.rows:
             raise ValueError("ROI outside the matrix")
         parent_uv = getattr(self, "uv_offset", 0) or self.rows * self.step
         m = GpuMat(h, w, self.cv_type, self.data + y * self.step + x * elem_size(self.cv_type), self.step, owner=self.owner)
@@ -281,14 +295,20 @@ def cast(in_type, out_type):
     return PointwiseIOp(in_type, out_type, [(capi.OP_CAST_TRUNC, cast_aux(out_type), None)])
 
 
-def read_nv12(mat, dsize=None, color_range=capi.YUV_FULL, primaries=capi.BT709, alpha=True, layout=capi.YUV_NV12):
+def read_nv12(mat, dsize=None, color_range=capi.YUV_FULL, primaries=capi.BT709, alpha=True, layout=capi.YUV_NV12, interp=INTER_LINEAR):
     """fk::ReadYUV<NV12> + fk::ConvertYUVToRGB<NV12, range, primaries, alpha, floatN>, optionally as the
     BackIOp of fk::Resize<INTER_LINEAR> (reference tests/resize/test_fused_resize.cu:141-143).
     `mat` is the CV_8UC1 luma view (rows = luma height); the UV plane follows it in memory.  layout = YUV_P010: the luma
     view is CV_16UC1 (10-bit codes in the high bits of 16-bit samples) and R, G, B come out on the 0..1023 scale.
     layout = YUV_YUYV / YUV_UYVY: `mat` is a packed 4:2:2 surface, CV_8UC2 (crops: GpuMat.yuv422_roi).
-    layout = YUV_I444: `mat` is the luma view of a planar 4:4:4 surface with uv_offset set (GpuMat.from_yuv444_tensor, yuv444_roi)."""
-    kind = capi.READ_NV12 if dsize is None else capi.READ_NV12_RESIZE_LINEAR
+    layout = YUV_I444: `mat` is the luma view of a planar 4:4:4 surface with uv_offset set (GpuMat.from_yuv444_tensor, yuv444_roi).
+    interp = INTER_AREA (with a dsize; NV12, NV21 and P010 surfaces): the box filter for surfaces and crops that shrink by large factors
+    (capi.READ_NV12_RESIZE_AREA: every luma and chroma sample of the view is weighted, the means are converted once)."""
+    if interp not in SUPPORTED_INTERPOLATIONS:
+        raise ValueError("Interpolation type not supported yet.")
+    if interp == INTER_AREA and dsize is None:
+        raise ValueError("INTER_AREA is a resize: read_nv12 needs a dsize for it")
+    kind = capi.READ_NV12 if dsize is None else _NV12_RESIZE_KIND[interp]
     mats = [mat] if isinstance(mat, GpuMat) else list(mat)  # a list = N crops (GpuMat.nv12_roi) of decoder surfaces, one launch
     if layout in (capi.YUV_YUYV, capi.YUV_UYVY):
         src_type = make_type(DEPTH_8U, 2)
@@ -756,12 +776,13 @@ def resize_boxes(frame, table, max_boxes, dsize, background=None, ar=IGNORE_AR, 
     """The batched read "resize from a device-built table of `frame`": batch = used_planes = max_boxes (validity is per plane, inside the
     table), and the chain states the whole frame's byte range (cvgs_plane_table_hull of the one whole-frame view) for the independence
     check of cvgs_execute_many.  yuv = (range, primaries, alpha) makes it the NV12 / NV21 read of a decoder surface.  interp = INTER_AREA
-    reads the SAME table (built with kind READ_RESIZE_LINEAR: one layout) through the box filter; pixel frames only."""
+    reads the SAME table (built with kind READ_RESIZE_LINEAR -- READ_NV12_RESIZE_LINEAR for a decoder surface: one layout) through the box
+    filter; with yuv the frame is the CV_8UC1 luma view of an NV12 / NV21 surface (READ_NV12_RESIZE_AREA)."""
     if interp not in SUPPORTED_INTERPOLATIONS:
         raise ValueError("Interpolation type not supported yet.")
-    if interp == INTER_AREA and yuv is not None:
-        raise ValueError("INTER_AREA reads pixel frames: there is no area variant of the NV12 kinds")
-    kind = capi.READ_NV12_RESIZE_LINEAR if yuv is not None else _RESIZE_KIND[interp]
+    if interp == INTER_AREA and yuv is not None and (frame.cv_type != make_type(DEPTH_8U, 1) or layout not in (capi.YUV_NV12, capi.YUV_NV21)):
+        raise ValueError("INTER_AREA over a device table reads pixel frames, or the CV_8UC1 luma view of an NV12 / NV21 surface")
+    kind = _NV12_RESIZE_KIND[interp] if yuv is not None else _RESIZE_KIND[interp]
     whole = ReadIOp(kind, frame.cv_type, [frame], 1, (int(dsize[0]), int(dsize[1])), ar, background, yuv)
     whole.yuv_layout = layout if yuv is not None else 0
     rd = ReadIOp(kind, frame.cv_type, None, int(max_boxes), (int(dsize[0]), int(dsize[1])), ar, background, yuv, table=_dev_ptr(table),

@@ -355,6 +355,24 @@ inline auto resize(const fk::YuvRead<PF, CR, CP, ALPHA, O, SW>& nv12Read, const 
     return fk::Resize<(fk::InterpolationType)INTER_F, (fk::AspectRatio)AR>::build(nv12Read, fk::Size(dsize.width, dsize.height), bg);
 }
 
+// resizeArea(thatIOp, dsize) / resizeArea<AR>(thatIOp, dsize, backgroundValue): the same fusion through the BOX FILTER (cv::INTER_AREA's
+// antialiasing; CVGS_READ_NV12_RESIZE_AREA, an engine extension) for surfaces and crops that shrink by large factors -- a 6K surface into a
+// 720p network input, detections of a 4K surface into 64 x 128.  Over the IOp of cvtColorNV12 (NV12), cvtColorP010 and the fk::NV21 reader;
+// the other layouts are refused when the chain is validated (CVGS_ERR_UNSUPPORTED).  A name of its own: resize<cv::INTER_AREA>(thatIOp, ...)
+// keeps failing to compile, as it always has.
+template <AspectRatio AR, fk::PixelFormat PF, fk::ColorRange CR, fk::ColorPrimitives CP, bool ALPHA, typename O, bool SW>
+inline auto resizeArea(const fk::YuvRead<PF, CR, CP, ALPHA, O, SW>& nv12Read, const cv::Size& dsize, const cv::Scalar& backgroundValue = cv::Scalar()) {
+    static_assert(PF == fk::NV12 || PF == fk::NV21 || PF == fk::P010, "resizeArea reads NV12, NV21 and P010 surfaces.");
+    const float bg[4] = {(float)backgroundValue[0], (float)backgroundValue[1], (float)backgroundValue[2], (float)backgroundValue[3]};
+    auto rd = fk::Resize<fk::INTER_LINEAR, (fk::AspectRatio)AR>::build(nv12Read, fk::Size(dsize.width, dsize.height), bg);
+    rd.kind = CVGS_READ_NV12_RESIZE_AREA; // the bilinear spelling's fields, unchanged
+    return rd;
+}
+template <fk::PixelFormat PF, fk::ColorRange CR, fk::ColorPrimitives CP, bool ALPHA, typename O, bool SW>
+inline auto resizeArea(const fk::YuvRead<PF, CR, CP, ALPHA, O, SW>& nv12Read, const cv::Size& dsize) {
+    return resizeArea<IGNORE_AR>(nv12Read, dsize);
+}
+
 // ---- warp (reference include/cvGPUSpeedup.cuh:267-442) --------------------------------------------------------------
 // warp<WT, InputType[, BATCH]>(input(s), FORWARD transform(s) as CV_64FC1 cv::Mat, dstSize(s)[, usedPlanes, defaultValue]):
 // the first IOp of a chain; its output is CV_32F of the input's channels.  The matrices are inverted on the host in

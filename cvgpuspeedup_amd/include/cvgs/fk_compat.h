@@ -623,11 +623,12 @@ template <typename Yuv> struct ResizeYuvRead {     // single image, NV12 read-ba
     Size dsize;
     int ar = CVGS_IGNORE_AR;            // cvGS::AspectRatio: PRESERVE_AR* letterboxes the surface into dsize
     float bg[4] = {0.f, 0.f, 0.f, 0.f}; // the padding value, in the read's output channel order
+    int kind = CVGS_READ_NV12_RESIZE_LINEAR; // or CVGS_READ_NV12_RESIZE_AREA (cvGS::resizeArea: NV12 / NV21 / P010 surfaces through the box filter)
     using OutputType = VectorType_t<float, cn<typename Yuv::OutputType>>;
     static constexpr Stage stage = Stage::Read;
     static_assert(Yuv::float_out, "Resize over an NV12 read-back interpolates in float: use ConvertYUVToRGB<..., floatN>");
     void lower(ChainBuilder& b) const {
-        back.lower_read(b, CVGS_READ_NV12_RESIZE_LINEAR);
+        back.lower_read(b, kind);
         b.d.read.dst_width = dsize.width; b.d.read.dst_height = dsize.height; b.d.read.aspect_ratio = ar;
         // the background enters BEFORE the R <-> B swap the BGR codes append (it runs through the program like a pixel)
         constexpr bool kSwap = Yuv::swap_rb;
@@ -829,7 +830,7 @@ template <InterpolationType IT, AspectRatio AR = IGNORE_AR> struct Resize {
     }
     template <PixelFormat PF, ColorRange CR, ColorPrimitives CP, bool ALPHA, typename O, bool SW>
     static auto build(const YuvRead<PF, CR, CP, ALPHA, O, SW>& back, const Size& dsize, const float* background = nullptr) {
-        static_assert(IT == INTER_LINEAR, "INTER_AREA over a YUV read-back is not implemented: there is no area variant of the NV12 read kinds (resize the converted image, or use INTER_LINEAR)");
+        static_assert(IT == INTER_LINEAR, "INTER_AREA over a YUV read-back is not implemented: there is no area variant of the NV12 read kinds under this spelling (resize the converted image, use INTER_LINEAR, or cvGS::resizeArea(nv12Read, dsize) for NV12 / NV21 / P010 surfaces: CVGS_READ_NV12_RESIZE_AREA)");
         ResizeYuvRead<YuvRead<PF, CR, CP, ALPHA, O, SW>> r{back, dsize};
         r.ar = (int)AR; // same numeric values as cvgs_aspect_ratio
         if (background)

@@ -152,8 +152,41 @@ typedef enum cvgs_read_kind {
      * Outside the window: background; planes z >= used_planes: the default value, then the chain's program -- as for the bilinear kind.
      * A view shrunk by exactly 2 on both axes gives the exact mean of each 2 x 2 block; a view as large as its target reproduces it.
      * Served by cvgs_execute, and one by one by cvgs_execute_many.  CVGS_ERR_UNSUPPORTED: CV_64F sources or values, mirrors, the
-     * descriptor queue, cvgs_circular_update; there is no AREA variant of the NV12 kinds.                                          */
-    CVGS_READ_RESIZE_AREA = 6
+     * descriptor queue, cvgs_circular_update.  Decoder surfaces have an AREA kind of their own, CVGS_READ_NV12_RESIZE_AREA below.       */
+    CVGS_READ_RESIZE_AREA = 6,
+    /* 7: reserved (CVGS_ERR_INVALID) */
+    /* INTER_AREA (box filter) resize of 4:2:0 DECODER SURFACES: an ENGINE EXTENSION.  For surfaces and crops that shrink by large factors
+     * (a 6K surface into 1280 x 720, detections of a 4K surface into 64 x 128), where the 2 x 2 taps of CVGS_READ_NV12_RESIZE_LINEAR alias.
+     * Uses the fields of CVGS_READ_NV12_RESIZE_LINEAR unchanged (views with uv_offset -- crops at even (x, y) -- or a device plane table,
+     * batch, used_planes, dst_width / dst_height, aspect_ratio, background, yuv_range / yuv_primaries / yuv_alpha / yuv_layout,
+     * table_src_lo / _hi); the value is that kind's: CV_32F with 3 or 4 channels, P010 on the 0..1023 scale.  Layouts: CVGS_YUV_NV12,
+     * CVGS_YUV_NV21, CVGS_YUV_P010; I420, YV12, YUYV, UYVY and I444 are CVGS_ERR_UNSUPPORTED.  Unlike the bilinear kind a view may have an
+     * ODD width or height (the last chroma sample then lies under one luma column / row only).  The plane table is BYTE FOR BYTE the table of
+     * the same chain spelled NV12_RESIZE_LINEAR: cvgs_plane_table_build / _bytes accept the kind, and a device table built for the bilinear
+     * NV12 kind -- by cvgs_plane_tables_from_boxes with read_kind = CVGS_READ_NV12_RESIZE_LINEAR too -- may be handed to an AREA chain
+     * (cvgs_plane_tables_from_boxes called with THIS kind is CVGS_ERR_UNSUPPORTED, as for CVGS_READ_RESIZE_AREA).  cvgs_plane_table_hull is,
+     * per plane, every luma byte of the view plus every chroma byte under it: ceil(h / 2) chroma rows of 2 * ceil(w / 2) samples.
+     * The arithmetic (the contract: strict fp32, no contraction, every operation rounded once, in this order).  Per axis, x given, y the same
+     * with fy, ty, h:
+     *   luma axis: exactly the axis rule of CVGS_READ_RESIZE_AREA with n = the view's luma extent w: the taps (i, wx_i), their sum Wx, and
+     *     the values a, b (shrinking) or s, i0 and the two weights w0, w1 (not shrinking).
+     *   chroma axis, over nc = (w + 1) >> 1 samples.  Shrinking (fx > 1.0f): ac = a * 0.5f, bc = b * 0.5f, c0 = min((int)floorf(ac), nc - 1),
+     *     c1 = max(min((int)ceilf(bc), nc), c0 + 1); for c = c0 .. c1-1 ascending wc = fminf((float)(c + 1), bc) - fmaxf((float)c, ac); if
+     *     bc <= ac the single tap (c0, 1.0f); Wcx = the fp32 sum of the weights, ascending, from 0.0f -- the same box seen from the chroma
+     *     grid: a chroma sample weighs half the luma area it sits under, and the last sample of an odd view gets its half weight by itself.
+     *     Not shrinking: the two taps (i0 >> 1, w0), (min(i0 + 1, w - 1) >> 1, w1) with the luma weights, both kept, in this order, even when
+     *     they name one sample; Wcx = 1.0f.
+     *   values: Ym = the AREA loop nest over the luma codes (rows ascending, row = row + v * wx over columns ascending, acc = acc + row * wy)
+     *     times 1.0f / (Wx * Wy); Um and Vm the same nest over the chroma taps of both axes times 1.0f / (Wcx * Wcy).  P010 codes are
+     *     sample >> 6, taken before any weighting.
+     *   conversion: (Ym, Um, Vm) go ONCE through the bilinear kind's per-tap conversion (cb = U - 128, cr = V - 128 -- 512 for P010 --,
+     *     yv = (Y - ysub) * yscale, R = yv + rv * cr, G = (yv + gu * cb) + gv * cr, B = yv + bu * cb), then alpha, the window / background /
+     *     default-value rules of the bilinear kind, then the chain's program.  The conversion is affine with no clamp: this equals "convert
+     *     every pixel, then box-filter" in exact arithmetic and differs from it by rounding only.
+     * A view as large as its target reproduces CVGS_READ_NV12's value; a view shrunk by exactly 2 converts the mean of each 2 x 2 luma block
+     * with its one chroma sample.  Served by cvgs_execute, and one by one by cvgs_execute_many.  CVGS_ERR_UNSUPPORTED, before anything is
+     * enqueued: CV_64F values, mirrors, the descriptor queue, cvgs_circular_update, CVGS_WRITE_NV12 behind it.                          */
+    CVGS_READ_NV12_RESIZE_AREA = 8
 } cvgs_read_kind;
 
 /* same numeric values as cvGS::AspectRatio (reference include/cvGPUSpeedup.cuh:32) */
@@ -326,7 +359,8 @@ typedef enum cvgs_write_kind {
      *   else: row padding stays untouched.  Planes z >= used_planes run the background value through the chain and are written like any other.
      * Served by cvgs_execute -- read kinds CVGS_READ_PIXEL, CVGS_READ_RESIZE_LINEAR, CVGS_READ_NV12, CVGS_READ_NV12_RESIZE_LINEAR with every
      *   source type and layout they take, host views or a device plane table, any fp32 program -- and one by one by cvgs_execute_many.
-     *   CVGS_ERR_UNSUPPORTED: CV_64F values, mirrors, warp reads, CVGS_READ_RESIZE_AREA, the descriptor queue, cvgs_circular_update.
+     *   CVGS_ERR_UNSUPPORTED: CV_64F values, mirrors, warp reads, CVGS_READ_RESIZE_AREA, CVGS_READ_NV12_RESIZE_AREA, the descriptor queue,
+     *   cvgs_circular_update.
      * Transcoding a surface at its own size with the same range and primaries in and out returns it byte for byte.                       */
     CVGS_WRITE_NV12 = 6
 } cvgs_write_kind;

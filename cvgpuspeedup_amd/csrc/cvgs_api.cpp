@@ -4,6 +4,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstdio>
@@ -19,6 +20,7 @@
 
 #include "cvgs_device.h"
 #include "cvgs_geometry.h"
+#include "cvgs_tick_overlap.h"
 
 using namespace cvgs;
 
@@ -36,9 +38,13 @@ const char* cvgs::bf16_kernel_name(const char* f16_name) {
 namespace {
 
 thread_local std::string g_err;
+// The note a successful cvgs_execute_many leaves for cvgs_last_error(): how its tick was launched (tick_note_text formats it on demand: the
+// call itself stores two words).  A failure's message replaces it.
+thread_local const char* g_tick_note = nullptr;
 
 int fail(int code, const std::string& msg) {
     g_err = msg;
+    g_tick_note = nullptr;
     return code;
 }
 
@@ -793,6 +799,11 @@ public:
             for (size_t i = 0; i < streams_.size(); ++i)
                 if (streams_[i]->stream == stream) { gone = streams_[i]; streams_.erase(streams_.begin() + (long)i); break; }
         }
+        {
+            std::lock_guard<std::mutex> lk(m_);
+            for (size_t i = 0; i < lanes_.size(); ++i)
+                if (lanes_[i].first == stream) { lanes_.erase(lanes_.begin() + (long)i); break; }
+        }
         if (!gone) return;
         {
             std::lock_guard<std::mutex> lk(gone->mu); // (a call of another thread still inside its launch on this stream finishes first)
@@ -842,9 +853,28 @@ public:
         }
         return nullptr;
     }
+    // The lanes of the ticks a capturing stream has taken (cvgs_tick_overlap.h), under the pool's lock: lanes_lock() first, then lanes(stream).
+    // Keyed by the stream handle; the state inside is tied to ONE capture id and starts over with the next.  No pinned memory, so a stream
+    // that only ever captures device-table ticks has no ManyStream.
+    std::unique_lock<std::mutex> lanes_lock() { return std::unique_lock<std::mutex>(m_); }
+    TickLanes& lanes(hipStream_t stream) {
+        for (auto& e : lanes_)
+            if (e.first == stream) return e.second;
+        if (lanes_.size() >= kMaxStreams) lanes_.erase(lanes_.begin()); // (the oldest entry: at worst one tick is captured in order)
+        lanes_.emplace_back(stream, TickLanes());
+        return lanes_.back().second;
+    }
+    // (lanes_lock() held) has another stream taken ticks of this capture?  A caller who alternates ticks over two streams has the two lanes
+    // already; four run slower than two (bench.py's two_streams leg: 2.50 against 2.31 us per frame)
+    bool lanes_on_other_streams(hipStream_t stream, unsigned long long capture_id) const {
+        for (const auto& e : lanes_)
+            if (e.first != stream && e.second.holds(capture_id)) return true;
+        return false;
+    }
 private:
     std::mutex m_;
     std::vector<ManyStream*> streams_;
+    std::vector<std::pair<hipStream_t, TickLanes>> lanes_;
 };
 ManyPool& many_pool() {
     static ManyPool* pool = new ManyPool; // leaked on purpose, as the descriptor scratch
@@ -1279,6 +1309,7 @@ struct TickPlan {
     TickCarrier carrier = TickCarrier::kernarg;
     size_t total_planes = 0;
     int max_batch = 0;
+    const char* why = nullptr; // family none: the reason, as cvgs_last_error() reports it after the call
 };
 // whatever the one-by-one path would serve must not fail because the chains happen to share a shape.
 //  * host descriptors under stream capture: a staged table is not capturable; one by one, chains of <= 64 planes travel in kernel
@@ -1287,17 +1318,17 @@ struct TickPlan {
 //  * chains that are not independent (one writes where another writes or reads): the fused launch runs them concurrently,
 //    n sequential cvgs_execute calls would not -- keep the sequential meaning.
 TickPlan plan_tick(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream) {
-    const TickPlan none;
-    if (n < 2 || n > CVGS_MAX_CHAINS) return none;
+    const auto refused = [](const char* why) { TickPlan no; no.why = why; return no; };
+    if (n < 2 || n > CVGS_MAX_CHAINS) return refused("not fused: one chain");
     const cvgs_chain_desc& c0 = chains[0];
     TickPlan plan;
     plan.family = c0.read.kind == CVGS_READ_PIXEL ? TickFamily::pointwise
                 : c0.read.kind == CVGS_READ_RESIZE_LINEAR ? TickFamily::k1
                 : c0.read.kind == CVGS_READ_NV12_RESIZE_LINEAR ? TickFamily::k4 : TickFamily::none;
-    if (plan.family == TickFamily::none) return none;
+    if (plan.family == TickFamily::none) return refused("not fused: no tick kernel for this read kind");
     const bool pw = plan.family == TickFamily::pointwise;
     const bool tables = (c0.read.flags & CVGS_READ_FLAG_TABLE_ON_DEVICE) != 0;
-    if (tables && plan.family != TickFamily::k1) return none; // per-pixel reads and K4's per-plane preconditions want the planes on the host
+    if (tables && plan.family != TickFamily::k1) return refused("not fused: device tables outside K1"); // per-pixel reads and K4's per-plane preconditions want the planes on the host
     int min_batch = 1;
     const cvgs_chain_desc* ptrs[CVGS_MAX_CHAINS];
     for (int i = 0; i < n; ++i) { // one shape (same_shape: kind, program, target extent), one descriptor form; the planes counted
@@ -1306,7 +1337,7 @@ TickPlan plan_tick(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream)
         if ((c.flags & (pw ? CVGS_CHAIN_FORCE_GENERIC | CVGS_CHAIN_NO_THREAD_FUSION : CVGS_CHAIN_FORCE_GENERIC)) ||
             (wk != CVGS_WRITE_TENSOR_SPLIT && wk != CVGS_WRITE_TENSOR_T_SPLIT && !(pw && wk == CVGS_WRITE_PIXEL_3D)) || !same_shape(c0, c) ||
             ((c.read.flags ^ c0.read.flags) & CVGS_READ_FLAG_TABLE_ON_DEVICE) != 0)
-            return none;
+            return refused("not fused: the chains differ in shape, target kind or descriptor form");
         plan.total_planes += (size_t)(c.read.batch > 0 ? c.read.batch : 0);
         plan.max_batch = std::max(plan.max_batch, (int)c.read.batch);
         min_batch = std::min(min_batch, (int)c.read.batch);
@@ -1321,12 +1352,13 @@ TickPlan plan_tick(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream)
                         is_yuv422(c0.read.yuv_layout) || is_yuv444(c0.read.yuv_layout));
     if (tables) plan.carrier = TickCarrier::device_tables;
     else if ((pw || (inline_ok && (k1_u8 || k4_il))) && plan.total_planes <= (size_t)cvgs::kManyInlineLarge) plan.carrier = TickCarrier::kernarg;
-    else if (pw) return none; // (the pointwise tick has no table form)
+    else if (pw) return refused("not fused: too many planes for a pointwise tick"); // (the pointwise tick has no table form)
     else plan.carrier = TickCarrier::host_table;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (plan.carrier == TickCarrier::host_table && hipStreamIsCapturing(stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return none;
-    if (min_batch < 1 || plan.max_batch > 65535 || (pw && (int64_t)n * plan.max_batch > 65535)) return none;
-    if (!chains_independent(ptrs, n)) return none;
+    if (plan.carrier == TickCarrier::host_table && hipStreamIsCapturing(stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return refused("not fused: host descriptors beyond the kernel arguments on a capturing stream");
+    if (min_batch < 1 || plan.max_batch > 65535 || (pw && (int64_t)n * plan.max_batch > 65535)) return refused("not fused: batch outside the grid's range");
+    if (!chains_independent(ptrs, n)) // (a device-table chain that states no hull and is not vouched for answers "not independent" too)
+        return refused(tables ? "not fused: chains not independent, or no hull stated (read.table_src_lo / _hi) and not vouched" : "not fused: chains not independent");
     return plan;
 }
 
@@ -1355,6 +1387,147 @@ bool tick_chain_fits(TickFamily family, const Lowered& L, const Lowered& L0) {
     for (size_t k = 0; k < L.planes.size() && (int)k < L.args.read.used; ++k)
         if (L.planes[k].w != L0.args.read.dst_w || L.planes[k].h != L0.args.read.dst_h) return false;
     return true;
+}
+
+// ---- a captured tick beside the ticks before it (cvgs_tick_overlap.h: the rule and the two-lane shape) -------------------------------------
+// One stream cannot overlap two ticks, and every tick pays ~3.9 us of launch floor, fill and drain while the memory system idles (DESIGN.md
+// section 5).  When a K1 tick over device tables is CAPTURED right behind another tick of this library and the stated byte ranges prove the two
+// lanes independent, the capture's dependency set is rewritten around the launch so that the graph gets two chains of ticks instead of one.
+// No stream, no event, nothing for an eager launch.  Counters and the last decision: cvgs_last_error() after a successful cvgs_execute_many.
+std::atomic<uint64_t> g_ticks_overlapped{0}, g_ticks_in_order{0};
+thread_local TickOverlap g_tick_why = TickOverlap::not_capturing;
+const char* const kTickNoteOverlap = "tick"; // g_tick_note: one fused launch, g_tick_why says how it was captured
+
+// What the overlap hides is the launch's fixed 3.9 us; two ticks side by side share the memory system and pay for it.  Measured on the headline's
+// crops (50 per frame to 64 x 128): ticks of 16 frames gain 3 %, ticks of 64 frames lose 2 % (profiles/tick_overlap_abab.txt).  The line is drawn
+// between the two, in output pixels: 1600 planes of 64 x 128.
+constexpr int64_t kTickOverlapMaxPixels = 1600ll * 64 * 128;
+
+bool tick_overlap_enabled() {
+    static const bool on = [] { const char* e = getenv("CVGS_TICK_OVERLAP"); return e ? e[0] != '0' : true; }();
+    return on;
+}
+
+// what the tick reads and writes, from the chains' own statements (chains_independent reads the same fields)
+void tick_footprint(const cvgs_chain_desc* chains, int n, const ManySeg* segs, TickFootprint& fp) {
+    fp.clear();
+    for (int i = 0; i < n; ++i) {
+        const cvgs_chain_desc& c = chains[i];
+        ByteRange out;
+        if (!tensor_out_range(c, &out)) { fp.unstated(); return; }
+        fp.write(out.lo, out.hi);
+        for (int m = 0; m < c.write.n_mirrors && c.write.mirrors; ++m)
+            fp.write(c.write.mirrors[m], c.write.mirrors[m] ? (const uint8_t*)c.write.mirrors[m] + (out.hi - out.lo) : nullptr);
+        fp.read(c.read.table_src_lo, c.read.table_src_hi); // (vouched but unstated: null, i.e. unknown)
+        fp.read(segs[i].table, segs[i].table ? segs[i].table + segs[i].batch : nullptr);
+    }
+}
+
+struct TickLaneCapture {
+    // Decides, and for an overlapped tick sets the stream's capture dependencies to the lane's.  Never fails: every refusal and every failed
+    // capture call leaves the stream as found and the tick in order.
+    void begin(const cvgs_chain_desc* chains, int n, const TickPlan& plan, const LaunchCtx& ctx, const ChainArgs& c, const ManySeg* segs, hipStream_t s) {
+        stream = s;
+        g_tick_why = TickOverlap::not_capturing;
+        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+        const hipGraphNode_t* deps = nullptr;
+        size_t n_deps = 0;
+        hipGraph_t graph = nullptr;
+        if (hipStreamGetCaptureInfo_v2(s, &st, &id, &graph, &deps, &n_deps) != hipSuccess) { (void)hipGetLastError(); return; }
+        if (st != hipStreamCaptureStatusActive) return;
+        capturing = true;
+        lock = many_pool().lanes_lock();
+        lanes = &many_pool().lanes(s);
+        found.assign((const TickNode*)deps, (const TickNode*)deps + n_deps);
+        if (!tick_overlap_enabled()) g_tick_why = TickOverlap::switched_off;
+        else if (plan.family != TickFamily::k1 || plan.carrier != TickCarrier::device_tables || ctx.done_word || ctx.stop_event || ctx.mirrors.n > 0 || c.write.data2)
+            g_tick_why = TickOverlap::not_k1_tables;
+        else if ((int64_t)plan.total_planes * c.read.dst_w * c.read.dst_h > kTickOverlapMaxPixels) g_tick_why = TickOverlap::large_tick;
+        else {
+            tick_footprint(chains, n, segs, fp);
+            planned = lanes->plan(id, found.data(), found.size(), fp);
+            g_tick_why = planned.why == TickOverlap::overlapped && many_pool().lanes_on_other_streams(s, id) ? TickOverlap::other_streams : planned.why;
+        }
+        if (g_tick_why != TickOverlap::overlapped) {
+            if (g_tick_why == TickOverlap::switched_off || g_tick_why == TickOverlap::not_k1_tables || g_tick_why == TickOverlap::large_tick) fp.unstated(); // nothing may run beside this one
+            return;
+        }
+        if (hipStreamUpdateCaptureDependencies(s, (hipGraphNode_t*)planned.deps.data(), planned.deps.size(), hipStreamSetCaptureDependencies) != hipSuccess) {
+            (void)hipGetLastError();
+            g_tick_why = TickOverlap::capture_call_failed;
+            (void)hipStreamUpdateCaptureDependencies(s, (hipGraphNode_t*)found.data(), found.size(), hipStreamSetCaptureDependencies); // as found
+            (void)hipGetLastError();
+            return;
+        }
+        rewritten = true;
+    }
+    // the launch was refused or failed: the stream's dependency set as found, nothing recorded
+    void abandon() {
+        if (rewritten) {
+            (void)hipStreamUpdateCaptureDependencies(stream, (hipGraphNode_t*)found.data(), found.size(), hipStreamSetCaptureDependencies);
+            (void)hipGetLastError();
+        }
+        if (lanes) lanes->drop();
+        release();
+    }
+    // The tick has been captured.  Overlapped: the other lane's last tick joins the frontier again.  0, or < 0 when the frontier could not
+    // be put back (the capture would no longer order later work behind both lanes).
+    int end() {
+        if (!capturing) return 0;
+        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+        const hipGraphNode_t* deps = nullptr;
+        size_t n_deps = 0;
+        unsigned long long id_now = 0;
+        TickNode node = nullptr;
+        if (hipStreamGetCaptureInfo_v2(stream, &st, &id_now, nullptr, &deps, &n_deps) == hipSuccess && st == hipStreamCaptureStatusActive && id_now == id && n_deps == 1) node = deps[0];
+        else (void)hipGetLastError();
+        int rc = 0;
+        if (rewritten) {
+            hipGraphNode_t beside = (hipGraphNode_t)planned.beside;
+            bool ok = node && hipStreamUpdateCaptureDependencies(stream, &beside, 1, hipStreamAddCaptureDependencies) == hipSuccess;
+            if (!ok) { // put the whole frontier back by hand: the tick (whatever the stream holds now) and everything found before it
+                (void)hipGetLastError();
+                std::vector<hipGraphNode_t> all((hipGraphNode_t*)found.data(), (hipGraphNode_t*)found.data() + found.size());
+                for (size_t i = 0; i < n_deps; ++i) all.push_back(deps[i]);
+                ok = hipStreamUpdateCaptureDependencies(stream, all.data(), all.size(), hipStreamSetCaptureDependencies) == hipSuccess;
+                if (!ok) (void)hipGetLastError();
+                lanes->drop();
+                g_tick_why = TickOverlap::capture_call_failed;
+                if (!ok) rc = fail(CVGS_ERR_HIP, "captured tick: the stream's capture dependencies could not be restored");
+            } else {
+                lanes->committed(planned, node, fp);
+            }
+        } else {
+            lanes->in_order(id, found.data(), found.size(), node, fp);
+        }
+        (g_tick_why == TickOverlap::overlapped ? g_ticks_overlapped : g_ticks_in_order).fetch_add(1, std::memory_order_relaxed);
+        release();
+        return rc;
+    }
+    ~TickLaneCapture() { release(); }
+private:
+    void release() {
+        lanes = nullptr;
+        capturing = rewritten = false;
+        if (lock.owns_lock()) lock.unlock();
+    }
+    hipStream_t stream = nullptr;
+    bool capturing = false, rewritten = false;
+    unsigned long long id = 0;
+    std::unique_lock<std::mutex> lock;
+    TickLanes* lanes = nullptr;
+    std::vector<TickNode> found;
+    TickFootprint fp;
+    TickLanes::Plan planned;
+};
+
+// cvgs_last_error() after a successful cvgs_execute_many: the call's note and the process-wide counters
+void tick_note_text(std::string& out) {
+    char counts[96];
+    std::snprintf(counts, sizeof(counts), " [captured ticks: %llu overlapped, %llu in order]", (unsigned long long)g_ticks_overlapped.load(),
+                  (unsigned long long)g_ticks_in_order.load());
+    out = g_tick_note == kTickNoteOverlap ? std::string("tick: ") + tick_overlap_text(g_tick_why) : std::string(g_tick_note);
+    out += counts;
 }
 
 // The planned tick: 1 launched / 0 not a fused launch after all (nothing was enqueued, and `table` has given back what it took) / < 0 error.
@@ -1391,9 +1564,17 @@ int launch_tick(const cvgs_chain_desc* chains, int32_t n, const TickPlan& plan, 
     if (rc) return rc;
     if (table.n_planes() > cvgs::kManyInlineLarge) return fail(CVGS_ERR_INVALID, "inline tick: more planes than counted");
     c.read.table = plan.carrier == TickCarrier::kernarg ? nullptr : segs[0].table; // non-null: the table variants; null + segments: planes in the arguments
+    TickLaneCapture lane; // on a capturing stream: beside the ticks before it when that is proven safe, else exactly as ever
+    lane.begin(chains, n, plan, ctx, c, segs, stream);
     rc = k4 ? launch_yuv_resize(c, table.planes(), table.n_planes(), 1 << 30, ctx, false, nullptr) : launch_k1(c, table.planes(), table.n_planes(), ctx, false, nullptr);
-    if (rc != 1) return fail(CVGS_ERR_HIP, "fused kernel launch failed");
+    if (rc != 1) {
+        lane.abandon();
+        return fail(CVGS_ERR_HIP, "fused kernel launch failed");
+    }
+    rc = lane.end();
     table.finish(true, &ctx);
+    if (rc) return rc;
+    g_tick_note = kTickNoteOverlap;
     return 1;
 }
 
@@ -1410,6 +1591,7 @@ int execute_many(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream) {
         rc = dispatch(&chains[i], L, stream, false, nullptr);
         if (rc) return rc;
     }
+    g_tick_note = plan.why ? plan.why : "not fused: the tick kernel does not take these chains"; // (an un-fused tick is not silent)
     return CVGS_OK;
 }
 
@@ -1592,7 +1774,13 @@ extern "C" {
 
 int cvgs_abi_version(void) { return CVGS_ABI_VERSION; }
 const char* cvgs_version_string(void) { return "cvgs-hip 0.2 (gfx950)"; }
-const char* cvgs_last_error(void) { return g_err.c_str(); }
+const char* cvgs_last_error(void) {
+    if (g_tick_note) { // a successful cvgs_execute_many left a note: how its tick was launched
+        tick_note_text(g_err);
+        g_tick_note = nullptr;
+    }
+    return g_err.c_str();
+}
 
 int cvgs_device_count(void) {
     int n = 0;

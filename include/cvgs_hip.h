@@ -25,7 +25,9 @@
  * kernel arguments allocates nothing, on the host or on the device, and can be captured.
  *
  * Return value: 0 (CVGS_OK) or a negative cvgs_status; cvgs_last_error() gives a thread-local
- * human-readable message.
+ * human-readable message.  After a SUCCESSFUL cvgs_execute_many it holds a note instead: how
+ * the tick was launched ("tick: ...", "not fused: <reason>") and, for captured ticks, how many
+ * this process has captured beside their predecessor / in order.
  */
 #ifndef CVGS_HIP_H
 #define CVGS_HIP_H

@@ -20,6 +20,7 @@
 
 #include "cvgs_device.h"
 #include "cvgs_geometry.h"
+#include "cvgs_tick_merge.h"
 #include "cvgs_tick_overlap.h"
 
 using namespace cvgs;
@@ -857,24 +858,31 @@ public:
     // Keyed by the stream handle; the state inside is tied to ONE capture id and starts over with the next.  No pinned memory, so a stream
     // that only ever captures device-table ticks has no ManyStream.
     std::unique_lock<std::mutex> lanes_lock() { return std::unique_lock<std::mutex>(m_); }
-    TickLanes& lanes(hipStream_t stream) {
+    TickLanes& lanes(hipStream_t stream) { return captured(stream).lanes; }
+    // Beside the lanes, under the same lock: the open node of the stream's merged ticks (cvgs_tick_merge.h) and the library's own copy of
+    // that node's launch (function, grid, argument block), from which the node is rewritten when a tick joins it.  Tied to ONE capture id
+    // like the lanes -- never to the node's address, which a later capture may recycle.
+    struct TickCaptured : TickCaptureRules {
+        std::unique_ptr<TickLaunchRecord> launch;
+    };
+    TickCaptured& captured(hipStream_t stream) {
         for (auto& e : lanes_)
             if (e.first == stream) return e.second;
         if (lanes_.size() >= kMaxStreams) lanes_.erase(lanes_.begin()); // (the oldest entry: at worst one tick is captured in order)
-        lanes_.emplace_back(stream, TickLanes());
+        lanes_.emplace_back(stream, TickCaptured());
         return lanes_.back().second;
     }
     // (lanes_lock() held) has another stream taken ticks of this capture?  A caller who alternates ticks over two streams has the two lanes
     // already; four run slower than two (bench.py's two_streams leg: 2.50 against 2.31 us per frame)
     bool lanes_on_other_streams(hipStream_t stream, unsigned long long capture_id) const {
         for (const auto& e : lanes_)
-            if (e.first != stream && e.second.holds(capture_id)) return true;
+            if (e.first != stream && (e.second.lanes.holds(capture_id) || e.second.merge.holds(capture_id))) return true;
         return false;
     }
 private:
     std::mutex m_;
     std::vector<ManyStream*> streams_;
-    std::vector<std::pair<hipStream_t, TickLanes>> lanes_;
+    std::vector<std::pair<hipStream_t, TickCaptured>> lanes_;
 };
 ManyPool& many_pool() {
     static ManyPool* pool = new ManyPool; // leaked on purpose, as the descriptor scratch
@@ -1521,11 +1529,171 @@ private:
     TickLanes::Plan planned;
 };
 
+// ---- a captured tick INSIDE the launch of the tick before it (cvgs_tick_merge.h: the rule and the shape) ----------------------------------
+// The two lanes hide part of a launch's fixed cost; a tick that joins the previous tick's kernel node pays none.  Ticks of at least
+// kTickMergeMinPixels take this path INSTEAD of the lanes: merged, or in order as a node of their own that the next tick may join (a merged
+// node is a large tick, and large ticks gain nothing side by side: kTickOverlapMaxPixels).  Smaller ticks, CVGS_TICK_MERGE=0, and every tick
+// the lanes would not admit either keep the lane code above, untouched.
+std::atomic<uint64_t> g_ticks_merged{0};
+thread_local TickMerge g_merge_why = TickMerge::first_tick;
+thread_local int g_merge_chains = 0;
+const char* const kTickNoteMerge = "tick-merge"; // g_tick_note: the tick took the merge path, g_merge_why says how it went
+
+bool tick_merge_enabled() {
+    static const bool on = [] { const char* e = getenv("CVGS_TICK_MERGE"); return e ? e[0] != '0' : true; }();
+    return on;
+}
+// Tuning / test hooks, read once: CVGS_TICK_MERGE_MIN_PIXELS moves the size floor (the suite's ticks are a few hundred pixels),
+// CVGS_TICK_MERGE_MAX_CHAINS lowers the cap (the 64-against-128 sweep); neither can raise the cap beyond the argument block's 128 segments.
+int64_t tick_merge_min_pixels() {
+    static const int64_t v = [] { const char* e = getenv("CVGS_TICK_MERGE_MIN_PIXELS"); return e && *e ? (int64_t)atoll(e) : kTickMergeMinPixels; }();
+    return v;
+}
+int tick_merge_max_chains() {
+    static const int v = [] {
+        const char* e = getenv("CVGS_TICK_MERGE_MAX_CHAINS");
+        const int n = e && *e ? atoi(e) : kTickMergeMaxChains;
+        return n < 2 ? 2 : (n > kTickMergeMaxChains ? kTickMergeMaxChains : n);
+    }();
+    return v;
+}
+
+struct TickMergeCapture {
+    enum { not_taken = 0, merged = 1, in_order = 2 };
+    // not_taken: the lanes decide, as ever.  merged: the tick rides in the previous tick's node, nothing is left to launch.  in_order: launch
+    // the tick as it is, then opened() (or abandon()).  Never fails: a refused graph call leaves the node as it was and the tick in order.
+    int begin(const cvgs_chain_desc* chains, int n, const TickPlan& plan, const LaunchCtx& ctx, const ChainArgs& c, const ManySeg* segs, hipStream_t s) {
+        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+        const hipGraphNode_t* deps = nullptr;
+        size_t n_deps = 0;
+        hipGraph_t graph = nullptr;
+        if (hipStreamGetCaptureInfo_v2(s, &st, &id, &graph, &deps, &n_deps) != hipSuccess) { (void)hipGetLastError(); return not_taken; }
+        if (st != hipStreamCaptureStatusActive) return not_taken;
+        lock = many_pool().lanes_lock();
+        state = &many_pool().captured(s);
+        // the lane rule's own admission (TickLaneCapture::begin), and the size floor
+        const bool admitted = plan.family == TickFamily::k1 && plan.carrier == TickCarrier::device_tables && !ctx.done_word && !ctx.stop_event && ctx.mirrors.n == 0 && !c.write.data2;
+        if (state->route(tick_merge_enabled(), admitted, (int64_t)plan.total_planes * c.read.dst_w * c.read.dst_h, tick_merge_min_pixels()) == TickPath::lanes) {
+            release();
+            return not_taken;
+        }
+        // what the tick would launch: the launch site builds its arguments and enqueues nothing
+        if (!mine) mine.reset(new TickLaunchRecord());
+        LaunchCtx probe(s);
+        probe.segs = segs;
+        probe.n_segs = n;
+        probe.record = mine.get();
+        probe.record_only = true;
+        const bool built = launch_k1(c, nullptr, 0, probe, false, nullptr) == 1 && mine->fn && mine->arg_ptrs;
+        tick_footprint(chains, n, segs, fp);
+        if (!built) fp.unstated(); // (a launch site that keeps no record: a node nothing joins)
+        key_of(*mine, key);
+        tick.fn = built ? mine->fn : nullptr;
+        tick.key = key.data();
+        tick.key_bytes = key.size();
+        tick.chains = n;
+        tick.max_batch = plan.max_batch;
+        tick.fp = &fp;
+        const TickNode* found = (const TickNode*)deps;
+        g_merge_why = state->merge.plan(id, found, n_deps, tick, tick_merge_max_chains());
+        if (g_merge_why == TickMerge::merged && many_pool().lanes_on_other_streams(s, id)) g_merge_why = TickMerge::other_streams;
+        if (g_merge_why == TickMerge::merged && !(state->launch && rewrite(*state->launch, (hipGraphNode_t)state->merge.node(), segs, n, plan.max_batch)))
+            g_merge_why = TickMerge::graph_call_failed;
+        if (g_merge_why != TickMerge::merged) return in_order;
+        state->merge.merged(tick);
+        g_merge_chains = state->merge.chains();
+        g_ticks_merged.fetch_add(1, std::memory_order_relaxed);
+        release();
+        return merged;
+    }
+    // the tick has been captured in order: its node (the stream's dependency set names it) is the one the next tick may join
+    void opened(hipStream_t s) {
+        if (!state) return;
+        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+        const hipGraphNode_t* deps = nullptr;
+        size_t n_deps = 0;
+        unsigned long long id_now = 0;
+        TickNode node = nullptr;
+        if (hipStreamGetCaptureInfo_v2(s, &st, &id_now, nullptr, &deps, &n_deps) == hipSuccess && st == hipStreamCaptureStatusActive && id_now == id && n_deps == 1) node = deps[0];
+        else (void)hipGetLastError();
+        state->merge.opened(id, node, tick);
+        state->launch.swap(mine); // the launch just captured is the record's (built by the dry run from the same arguments)
+        g_ticks_in_order.fetch_add(1, std::memory_order_relaxed);
+        release();
+    }
+    void abandon() {
+        if (state) state->merge.drop();
+        release();
+    }
+    ~TickMergeCapture() { release(); }
+private:
+    // every tick of a node shares these bytes: the chain arguments without what each segment carries, and the geometry likewise
+    static void key_of(const TickLaunchRecord& r, std::vector<unsigned char>& out) {
+        ChainArgs c = r.a.c;
+        c.read.batch = c.read.used = 0;
+        c.read.table = nullptr;
+        c.write.data = nullptr;
+        out.resize(sizeof(ChainArgs) + TickLaunchRecord::kGeomBytes + 3 * sizeof(unsigned));
+        std::memcpy(out.data(), &c, sizeof(ChainArgs));
+        std::memcpy(out.data() + sizeof(ChainArgs), r.geom_key, TickLaunchRecord::kGeomBytes);
+        const unsigned shape[3] = {r.grid[0], r.block, (unsigned)r.geom_bytes}; // (grid y and z are what merging changes)
+        std::memcpy(out.data() + sizeof(ChainArgs) + TickLaunchRecord::kGeomBytes, shape, sizeof(shape));
+    }
+    // The node's launch with the tick's segments behind its own: a copy is changed, the node rewritten from the copy, and the copy kept only
+    // when the runtime took it.  Pointers the runtime hands back (hipGraphKernelNodeGetParams) are never used.
+    static bool rewrite(TickLaunchRecord& rec, hipGraphNode_t node, const ManySeg* segs, int n, int max_batch) {
+        const int have = (int)rec.grid[2];
+        if (!node || !rec.fn || !rec.arg_ptrs || have < 1 || have + n > CVGS_MAX_CHAINS) return false;
+        static thread_local std::unique_ptr<TickLaunchRecord> next;
+        if (!next) next.reset(new TickLaunchRecord());
+        *next = rec;
+        for (int i = 0; i < n; ++i) next->a.seg[have + i] = segs[i];
+        next->grid[2] = (unsigned)(have + n);
+        if ((unsigned)max_batch > next->grid[1]) next->grid[1] = (unsigned)max_batch;
+        next->a.c.read.batch = (int32_t)next->grid[1];
+        void* args[kTickLaunchArgs];
+        next->arg_ptrs(*next, args);
+        hipKernelNodeParams p{};
+        p.func = const_cast<void*>(next->fn);
+        p.gridDim = dim3(next->grid[0], next->grid[1], next->grid[2]);
+        p.blockDim = dim3(next->block);
+        p.sharedMemBytes = 0;
+        p.kernelParams = args; // (copied by the call)
+        p.extra = nullptr;
+        if (hipGraphKernelNodeSetParams(node, &p) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        rec = *next;
+        return true;
+    }
+    void release() {
+        state = nullptr;
+        if (lock.owns_lock()) lock.unlock();
+    }
+    unsigned long long id = 0;
+    std::unique_lock<std::mutex> lock;
+    ManyPool::TickCaptured* state = nullptr;
+    std::unique_ptr<TickLaunchRecord> mine;
+    std::vector<unsigned char> key;
+    TickFootprint fp;
+    TickMergeTick tick;
+};
+
 // cvgs_last_error() after a successful cvgs_execute_many: the call's note and the process-wide counters
 void tick_note_text(std::string& out) {
     char counts[96];
     std::snprintf(counts, sizeof(counts), " [captured ticks: %llu overlapped, %llu in order]", (unsigned long long)g_ticks_overlapped.load(),
                   (unsigned long long)g_ticks_in_order.load());
+    if (g_tick_note == kTickNoteMerge) { // the merge path: its own words, and the third counter in front of the two
+        char text[160];
+        if (g_merge_why == TickMerge::merged) std::snprintf(text, sizeof(text), "tick: %s (%d chains)", tick_merge_text(g_merge_why), g_merge_chains);
+        else std::snprintf(text, sizeof(text), "tick: %s", tick_merge_text(g_merge_why));
+        char merged[64];
+        std::snprintf(merged, sizeof(merged), " [merged ticks: %llu]", (unsigned long long)g_ticks_merged.load());
+        out = std::string(text) + merged + counts;
+        return;
+    }
     out = g_tick_note == kTickNoteOverlap ? std::string("tick: ") + tick_overlap_text(g_tick_why) : std::string(g_tick_note);
     out += counts;
 }
@@ -1564,17 +1732,28 @@ int launch_tick(const cvgs_chain_desc* chains, int32_t n, const TickPlan& plan, 
     if (rc) return rc;
     if (table.n_planes() > cvgs::kManyInlineLarge) return fail(CVGS_ERR_INVALID, "inline tick: more planes than counted");
     c.read.table = plan.carrier == TickCarrier::kernarg ? nullptr : segs[0].table; // non-null: the table variants; null + segments: planes in the arguments
-    TickLaneCapture lane; // on a capturing stream: beside the ticks before it when that is proven safe, else exactly as ever
-    lane.begin(chains, n, plan, ctx, c, segs, stream);
+    // on a capturing stream: inside the previous tick's launch, or beside the ticks before it, when that is proven safe -- else exactly as ever
+    TickMergeCapture merge;
+    const int merging = k4 ? TickMergeCapture::not_taken : merge.begin(chains, n, plan, ctx, c, segs, stream);
+    if (merging == TickMergeCapture::merged) {
+        table.finish(true, &ctx);
+        g_tick_note = kTickNoteMerge;
+        return 1;
+    }
+    TickLaneCapture lane;
+    if (merging == TickMergeCapture::not_taken) lane.begin(chains, n, plan, ctx, c, segs, stream);
     rc = k4 ? launch_yuv_resize(c, table.planes(), table.n_planes(), 1 << 30, ctx, false, nullptr) : launch_k1(c, table.planes(), table.n_planes(), ctx, false, nullptr);
     if (rc != 1) {
         lane.abandon();
+        merge.abandon();
         return fail(CVGS_ERR_HIP, "fused kernel launch failed");
     }
-    rc = lane.end();
+    rc = 0;
+    if (merging == TickMergeCapture::in_order) merge.opened(stream);
+    else rc = lane.end();
     table.finish(true, &ctx);
     if (rc) return rc;
-    g_tick_note = kTickNoteOverlap;
+    g_tick_note = merging == TickMergeCapture::in_order ? kTickNoteMerge : kTickNoteOverlap;
     return 1;
 }
 

@@ -130,6 +130,7 @@ struct MirrorArgs {          // 64 bytes
 };
 
 struct ManySeg;
+struct TickLaunchRecord;
 // What a K1 / K4 launch takes beside its chain: ONE explicit argument from the C-ABI call down to the launch site (round 6; rounds 4-5 passed
 // these through three thread-local slots, and a launch site that forgot to consume one fell back to a stream synchronise).
 struct LaunchCtx {
@@ -147,6 +148,11 @@ struct LaunchCtx {
     uint64_t* done_word = nullptr;
     uint64_t done_value = 0;
     bool done_word_taken = false;
+    // A K1 launch over device tables into a planar tensor hands back what it launches (function, grid, its argument block: TickLaunchRecord
+    // below) when asked to; record_only: it builds all that and enqueues NOTHING (a launch site that cannot record then fails the call).
+    // cvgs_api.cpp rewrites a captured tick's graph node from such a record when the next tick joins its launch (cvgs_tick_merge.h).
+    TickLaunchRecord* record = nullptr;
+    bool record_only = false;
     LaunchCtx() = default;
     explicit LaunchCtx(void* s) : stream(s) {}
 };
@@ -163,6 +169,25 @@ struct KernArgsMany {
     ManySeg seg[CVGS_MAX_CHAINS];
 };
 static_assert(sizeof(KernArgsMany) <= 4096 - 256, "segment block + K1Geom must fit the kernel-argument block");
+// One K1 table launch as its launch site built it (LaunchCtx::record): the library's OWN copy of every kernel argument, so that the graph node
+// of a captured tick can be rewritten later without reading anything back from the runtime.
+struct TickLaunchRecord {
+    const void* fn = nullptr;      // the kernel function
+    unsigned grid[3] = {0, 0, 0};
+    unsigned block = 0;
+    // the leading scalar parameters that repeat segment 0 (k_k1_impl.hpp: K1_PRELOADED_PARAMS; the others repeat fields of the geometry)
+    const PlaneParams* pre_table = nullptr;
+    uint8_t* pre_out = nullptr;
+    int32_t pre_batch = 0, pre_used = 0;
+    KernArgsMany a;
+    static constexpr size_t kGeomBytes = 256;
+    alignas(16) unsigned char geom[kGeomBytes];     // the launch's K1Geom
+    alignas(16) unsigned char geom_key[kGeomBytes]; // the same without what a segment carries (the tensor, `used`): equal for ticks that may share a launch
+    size_t geom_bytes = 0;
+    // fills the kernel's argument-pointer array (12 entries, parameter order) with addresses INSIDE this record
+    void (*arg_ptrs)(TickLaunchRecord& r, void** args) = nullptr;
+};
+static constexpr int kTickLaunchArgs = 12;
 // Fused chains described on the HOST (fresh crop lists every tick): the planes of ALL chains travel in the kernel arguments behind the
 // segment block (ManySeg::table then holds the chain's first index into `planes`, not an address).  The runtime places kernel arguments
 // in device memory, so the kernel reads its descriptors as it reads a device table -- a pinned host table costs every XCD a PCIe round

@@ -392,6 +392,14 @@ struct ProbeWorklist { const uint32_t* base = nullptr; uint32_t slots = 0; };
 inline ProbeWorklist& probe_worklist() { static ProbeWorklist w; return w; }
 #endif
 
+// the argument-pointer array of a recorded table launch, in the kernel's parameter order, every address inside the record
+static inline void k1_record_arg_ptrs(TickLaunchRecord& r, void** args) {
+    K1Geom& g = *reinterpret_cast<K1Geom*>(r.geom);
+    void* const p[kTickLaunchArgs] = {(void*)&r.pre_table, (void*)&r.pre_out, (void*)&g.img_stride, (void*)&g.ch_stride, (void*)&r.pre_batch, (void*)&r.pre_used,
+                                      (void*)&g.col_tiles, (void*)&g.dst_w, (void*)&g.dst_h, (void*)&g.out_w, (void*)&r.a, (void*)&g};
+    for (int i = 0; i < kTickLaunchArgs; ++i) args[i] = p[i];
+}
+
 template <int CN, int NPL, int RPW, class Prog, int SRC, typename OT, int WM = WM_PLANAR, bool MIR = false>
 static hipError_t launch_t(const ChainArgs& c, const PlaneParams* inline_planes, int n_inline, int out_cn, LaunchCtx& x) {
     hipStream_t stream = (hipStream_t)x.stream;
@@ -482,6 +490,28 @@ static hipError_t launch_t(const ChainArgs& c, const PlaneParams* inline_planes,
     void* args[] = {(void*)&pre_table, (void*)&pre_out, (void*)&g.img_stride, (void*)&g.ch_stride, (void*)&pre_batch, (void*)&pre_used, (void*)&g.col_tiles,
                     (void*)&g.dst_w, (void*)&g.dst_h, (void*)&g.out_w, (void*)&a, (void*)&g};
     const void* fn = (const void*)&k1_resize_split<CN, NPL, RPW, Prog, SRC, OT, WM, MIR>;
+    if constexpr (NPL == 0 && WM == WM_PLANAR && !MIR) {
+        if (x.record) { // the launch as it stands, in the caller's keeping (cvgs_device.h: TickLaunchRecord)
+            TickLaunchRecord& r = *x.record;
+            static_assert(sizeof(K1Geom) <= TickLaunchRecord::kGeomBytes, "TickLaunchRecord::geom holds a K1Geom");
+            r.fn = fn;
+            r.grid[0] = grid.x, r.grid[1] = grid.y, r.grid[2] = grid.z;
+            r.block = 64 * kK1Waves;
+            r.pre_table = pre_table, r.pre_out = pre_out, r.pre_batch = pre_batch, r.pre_used = pre_used;
+            r.a = a;
+            K1Geom key = g; // this kernel takes the tensor and `used` from the segment, never from the geometry
+            key.out = nullptr;
+            key.used = 0;
+            std::memset(r.geom, 0, sizeof(r.geom));
+            std::memset(r.geom_key, 0, sizeof(r.geom_key));
+            std::memcpy(r.geom, &g, sizeof(g));
+            std::memcpy(r.geom_key, &key, sizeof(key));
+            r.geom_bytes = sizeof(g);
+            r.arg_ptrs = &k1_record_arg_ptrs;
+            if (x.record_only) return hipSuccess;
+        }
+    }
+    if (x.record_only) return hipErrorNotSupported; // (asked to build a record this launch site does not keep: nothing is enqueued)
     hipError_t e;
     if (x.stop_event && !x.stop_event_taken) {
         x.stop_event_taken = true;

@@ -27,7 +27,8 @@
  * Return value: 0 (CVGS_OK) or a negative cvgs_status; cvgs_last_error() gives a thread-local
  * human-readable message.  After a SUCCESSFUL cvgs_execute_many it holds a note instead: how
  * the tick was launched ("tick: ...", "not fused: <reason>") and, for captured ticks, how many
- * this process has captured beside their predecessor / in order.
+ * this process has captured beside their predecessor / in order (and, for a tick that was merged
+ * into the previous tick's launch or was tried for it, how many were merged).
  */
 #ifndef CVGS_HIP_H
 #define CVGS_HIP_H
@@ -458,7 +459,11 @@ int cvgs_execute(const cvgs_chain_desc* chain, cvgs_stream_t stream);
  * hipStreamDestroy continues the old ring: destroy a stream only once its fused launches have finished); pass device plane tables to
  * make such a fused call capturable; at most
  * CVGS_MAX_CHAINS chains per call.  The reference's closest spelling is the batch sweep of
- * tests/batchresize/test_batchresize_x_split3D.cu:384-392 (one launch per BATCH value).                          */
+ * tests/batchresize/test_batchresize_x_split3D.cu:384-392 (one launch per BATCH value).
+ * On a CAPTURING stream a K1 tick over device tables may add no kernel node at all: when it follows this library's previous tick of the
+ * same capture directly, launches the same kernel over an equal argument block and is proven independent of it from the stated ranges, its
+ * chains join that tick's node (gridDim.z grows; up to CVGS_MAX_CHAINS chains per node; CVGS_TICK_MERGE=0 keeps one node per tick).  The
+ * node is then this library's: do not change its parameters.  DESIGN.md section 5.                                                       */
 int cvgs_execute_many(const cvgs_chain_desc* chains, int32_t n_chains, cvgs_stream_t stream);
 
 /* Call before destroying a stream that has carried cvgs_execute_many calls with host descriptors: waits for the stream's work

@@ -20,8 +20,7 @@
 
 #include "cvgs_device.h"
 #include "cvgs_geometry.h"
-#include "cvgs_tick_merge.h"
-#include "cvgs_tick_overlap.h"
+#include "cvgs_tick_capture.h"
 
 using namespace cvgs;
 
@@ -39,14 +38,24 @@ const char* cvgs::bf16_kernel_name(const char* f16_name) {
 namespace {
 
 thread_local std::string g_err;
-// The note a successful cvgs_execute_many leaves for cvgs_last_error(): how its tick was launched (tick_note_text formats it on demand: the
-// call itself stores two words).  A failure's message replaces it.
-thread_local const char* g_tick_note = nullptr;
+// The note a successful cvgs_execute_many leaves for cvgs_last_error(): how its tick was launched (cvgs_tick_capture.h; tick_note_text formats
+// it on demand).  A failure's message replaces it.
+thread_local TickNote g_tick_note;
 
 int fail(int code, const std::string& msg) {
     g_err = msg;
-    g_tick_note = nullptr;
+    g_tick_note = TickNote();
     return code;
+}
+
+// Switches and tuning / test hooks of the environment; every caller keeps the value in a static of its own: each is read once.
+bool env_flag(const char* name) { // on unless the value starts with 0
+    const char* e = getenv(name);
+    return e ? e[0] != '0' : true;
+}
+int64_t env_int(const char* name, int64_t fallback) {
+    const char* e = getenv(name);
+    return e && *e ? (int64_t)atoll(e) : fallback;
 }
 
 int hip_fail(hipError_t e, const char* what) {
@@ -556,10 +565,7 @@ int lower(const cvgs_chain_desc* ch, bool circular, Lowered& L) {
 // cvgs_execute_many 47.3 -> 43.9 us, one chain of 400 crops 28.0 -> 23.7 us (host enqueue 19.4 -> 14.0 us); 300 back-to-back
 // launches with a different crop list each through recycled slots verified plane by plane against the oracle.
 static bool scratch_zero_copy() {
-    static const bool on = [] {
-        const char* e = getenv("CVGS_SCRATCH_ZEROCOPY");
-        return e ? e[0] != '0' : true;
-    }();
+    static const bool on = env_flag("CVGS_SCRATCH_ZEROCOPY");
     return on;
 }
 
@@ -799,11 +805,8 @@ public:
             std::lock_guard<std::mutex> lk(m_);
             for (size_t i = 0; i < streams_.size(); ++i)
                 if (streams_[i]->stream == stream) { gone = streams_[i]; streams_.erase(streams_.begin() + (long)i); break; }
-        }
-        {
-            std::lock_guard<std::mutex> lk(m_);
-            for (size_t i = 0; i < lanes_.size(); ++i)
-                if (lanes_[i].first == stream) { lanes_.erase(lanes_.begin() + (long)i); break; }
+            for (size_t i = 0; i < captured_.size(); ++i)
+                if (captured_[i].first == stream) { captured_.erase(captured_.begin() + (long)i); break; }
         }
         if (!gone) return;
         {
@@ -854,35 +857,29 @@ public:
         }
         return nullptr;
     }
-    // The lanes of the ticks a capturing stream has taken (cvgs_tick_overlap.h), under the pool's lock: lanes_lock() first, then lanes(stream).
-    // Keyed by the stream handle; the state inside is tied to ONE capture id and starts over with the next.  No pinned memory, so a stream
-    // that only ever captures device-table ticks has no ManyStream.
-    std::unique_lock<std::mutex> lanes_lock() { return std::unique_lock<std::mutex>(m_); }
-    TickLanes& lanes(hipStream_t stream) { return captured(stream).lanes; }
-    // Beside the lanes, under the same lock: the open node of the stream's merged ticks (cvgs_tick_merge.h) and the library's own copy of
-    // that node's launch (function, grid, argument block), from which the node is rewritten when a tick joins it.  Tied to ONE capture id
-    // like the lanes -- never to the node's address, which a later capture may recycle.
-    struct TickCaptured : TickCaptureRules {
-        std::unique_ptr<TickLaunchRecord> launch;
-    };
-    TickCaptured& captured(hipStream_t stream) {
-        for (auto& e : lanes_)
+    // What the ticks a capturing stream has taken left behind: the lanes (cvgs_tick_overlap.h), the open merged node (cvgs_tick_merge.h) and
+    // the library's copy of that node's launch (function, grid, argument block).  Under the pool's lock: captured_lock() first, then
+    // captured(stream) -- the driver of cvgs_tick_capture.h does both.  Keyed by the stream handle; the state inside is tied to ONE capture id
+    // and starts over with the next.  No pinned memory, so a stream that only ever captures device-table ticks has no ManyStream.
+    std::unique_lock<std::mutex> captured_lock() { return std::unique_lock<std::mutex>(m_); }
+    TickCaptured<TickLaunchRecord>& captured(hipStream_t stream) {
+        for (auto& e : captured_)
             if (e.first == stream) return e.second;
-        if (lanes_.size() >= kMaxStreams) lanes_.erase(lanes_.begin()); // (the oldest entry: at worst one tick is captured in order)
-        lanes_.emplace_back(stream, TickCaptured());
-        return lanes_.back().second;
+        if (captured_.size() >= kMaxStreams) captured_.erase(captured_.begin()); // (the oldest entry: at worst one tick is captured in order)
+        captured_.emplace_back(stream, TickCaptured<TickLaunchRecord>());
+        return captured_.back().second;
     }
-    // (lanes_lock() held) has another stream taken ticks of this capture?  A caller who alternates ticks over two streams has the two lanes
+    // (captured_lock() held) has another stream taken ticks of this capture?  A caller who alternates ticks over two streams has the two lanes
     // already; four run slower than two (bench.py's two_streams leg: 2.50 against 2.31 us per frame)
-    bool lanes_on_other_streams(hipStream_t stream, unsigned long long capture_id) const {
-        for (const auto& e : lanes_)
+    bool captured_on_other_streams(hipStream_t stream, unsigned long long capture_id) const {
+        for (const auto& e : captured_)
             if (e.first != stream && (e.second.lanes.holds(capture_id) || e.second.merge.holds(capture_id))) return true;
         return false;
     }
 private:
     std::mutex m_;
     std::vector<ManyStream*> streams_;
-    std::vector<std::pair<hipStream_t, TickCaptured>> lanes_;
+    std::vector<std::pair<hipStream_t, TickCaptured<TickLaunchRecord>>> captured_;
 };
 ManyPool& many_pool() {
     static ManyPool* pool = new ManyPool; // leaked on purpose, as the descriptor scratch
@@ -965,7 +962,7 @@ struct TickTable {
             args = &planes;
             return 0;
         }
-        static const bool progress_word = [] { const char* e = getenv("CVGS_MANY_PROGRESS_WORD"); return e ? e[0] != '0' : true; }();
+        static const bool progress_word = env_flag("CVGS_MANY_PROGRESS_WORD");
         if (progress_word && (ms = many_pool().get(s, stream_device(s))) != nullptr) {
             ms_lock = std::unique_lock<std::mutex>(ms->mu);
             mslot = many_pool().acquire(ms, bytes);
@@ -1353,7 +1350,7 @@ TickPlan plan_tick(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream)
     }
     // host-described K1 chains of u8 pixels with 3 / 4 channels, K4 chains of interleaved chroma / packed 4:2:2 / planar 4:4:4, pointwise chains:
     // at most kManyInlineLarge planes in all travel in the kernel arguments (cvgs_device.h: KernArgsManyInline)
-    static const bool inline_ok = [] { const char* e = getenv("CVGS_MANY_INLINE"); return e ? e[0] != '0' : true; }();
+    static const bool inline_ok = env_flag("CVGS_MANY_INLINE");
     const bool k1_u8 = plan.family == TickFamily::k1 && CVGS_TYPE_CN(c0.read.src_type) >= 3 && CVGS_TYPE_DEPTH(c0.read.src_type) == CVGS_DEPTH_8U;
     const bool k4_il = plan.family == TickFamily::k4 &&
                        (c0.read.yuv_layout == CVGS_YUV_NV12 || c0.read.yuv_layout == CVGS_YUV_NV21 || c0.read.yuv_layout == CVGS_YUV_P010 ||
@@ -1397,24 +1394,13 @@ bool tick_chain_fits(TickFamily family, const Lowered& L, const Lowered& L0) {
     return true;
 }
 
-// ---- a captured tick beside the ticks before it (cvgs_tick_overlap.h: the rule and the two-lane shape) -------------------------------------
+// ---- a captured tick beside the ticks before it, or inside the previous tick's launch -------------------------------------------------------
 // One stream cannot overlap two ticks, and every tick pays ~3.9 us of launch floor, fill and drain while the memory system idles (DESIGN.md
-// section 5).  When a K1 tick over device tables is CAPTURED right behind another tick of this library and the stated byte ranges prove the two
-// lanes independent, the capture's dependency set is rewritten around the launch so that the graph gets two chains of ticks instead of one.
-// No stream, no event, nothing for an eager launch.  Counters and the last decision: cvgs_last_error() after a successful cvgs_execute_many.
-std::atomic<uint64_t> g_ticks_overlapped{0}, g_ticks_in_order{0};
-thread_local TickOverlap g_tick_why = TickOverlap::not_capturing;
-const char* const kTickNoteOverlap = "tick"; // g_tick_note: one fused launch, g_tick_why says how it was captured
-
-// What the overlap hides is the launch's fixed 3.9 us; two ticks side by side share the memory system and pay for it.  Measured on the headline's
-// crops (50 per frame to 64 x 128): ticks of 16 frames gain 3 %, ticks of 64 frames lose 2 % (profiles/tick_overlap_abab.txt).  The line is drawn
-// between the two, in output pixels: 1600 planes of 64 x 128.
-constexpr int64_t kTickOverlapMaxPixels = 1600ll * 64 * 128;
-
-bool tick_overlap_enabled() {
-    static const bool on = [] { const char* e = getenv("CVGS_TICK_OVERLAP"); return e ? e[0] != '0' : true; }();
-    return on;
-}
+// section 5).  When a K1 tick over device tables is CAPTURED right behind another tick of this library and the stated byte ranges prove it
+// independent of them, it is captured beside them (cvgs_tick_overlap.h: the capture's dependency set is rewritten around the launch, the
+// graph gets two chains of ticks) or, from kTickMergeMinPixels on, inside the previous tick's kernel node (cvgs_tick_merge.h: it pays no
+// launch at all).  The driver of both rules, the thresholds, the counters and the note are cvgs_tick_capture.h's, host only; here is what
+// needs HIP or the chain descriptors.  No stream, no event, nothing for an eager launch.
 
 // what the tick reads and writes, from the chains' own statements (chains_independent reads the same fields)
 void tick_footprint(const cvgs_chain_desc* chains, int n, const ManySeg* segs, TickFootprint& fp) {
@@ -1431,217 +1417,27 @@ void tick_footprint(const cvgs_chain_desc* chains, int n, const ManySeg* segs, T
     }
 }
 
-struct TickLaneCapture {
-    // Decides, and for an overlapped tick sets the stream's capture dependencies to the lane's.  Never fails: every refusal and every failed
-    // capture call leaves the stream as found and the tick in order.
-    void begin(const cvgs_chain_desc* chains, int n, const TickPlan& plan, const LaunchCtx& ctx, const ChainArgs& c, const ManySeg* segs, hipStream_t s) {
-        stream = s;
-        g_tick_why = TickOverlap::not_capturing;
+// The capturing stream as the driver sees it, and the tick's segments for the node it may join.
+struct HipTickStream {
+    using Launch = TickLaunchRecord;
+    hipStream_t stream;
+    const ManySeg* segs;
+    int n, max_batch;
+    bool info(unsigned long long& id, std::vector<TickNode>& deps) {
         hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        const hipGraphNode_t* deps = nullptr;
-        size_t n_deps = 0;
-        hipGraph_t graph = nullptr;
-        if (hipStreamGetCaptureInfo_v2(s, &st, &id, &graph, &deps, &n_deps) != hipSuccess) { (void)hipGetLastError(); return; }
-        if (st != hipStreamCaptureStatusActive) return;
-        capturing = true;
-        lock = many_pool().lanes_lock();
-        lanes = &many_pool().lanes(s);
-        found.assign((const TickNode*)deps, (const TickNode*)deps + n_deps);
-        if (!tick_overlap_enabled()) g_tick_why = TickOverlap::switched_off;
-        else if (plan.family != TickFamily::k1 || plan.carrier != TickCarrier::device_tables || ctx.done_word || ctx.stop_event || ctx.mirrors.n > 0 || c.write.data2)
-            g_tick_why = TickOverlap::not_k1_tables;
-        else if ((int64_t)plan.total_planes * c.read.dst_w * c.read.dst_h > kTickOverlapMaxPixels) g_tick_why = TickOverlap::large_tick;
-        else {
-            tick_footprint(chains, n, segs, fp);
-            planned = lanes->plan(id, found.data(), found.size(), fp);
-            g_tick_why = planned.why == TickOverlap::overlapped && many_pool().lanes_on_other_streams(s, id) ? TickOverlap::other_streams : planned.why;
-        }
-        if (g_tick_why != TickOverlap::overlapped) {
-            if (g_tick_why == TickOverlap::switched_off || g_tick_why == TickOverlap::not_k1_tables || g_tick_why == TickOverlap::large_tick) fp.unstated(); // nothing may run beside this one
-            return;
-        }
-        if (hipStreamUpdateCaptureDependencies(s, (hipGraphNode_t*)planned.deps.data(), planned.deps.size(), hipStreamSetCaptureDependencies) != hipSuccess) {
-            (void)hipGetLastError();
-            g_tick_why = TickOverlap::capture_call_failed;
-            (void)hipStreamUpdateCaptureDependencies(s, (hipGraphNode_t*)found.data(), found.size(), hipStreamSetCaptureDependencies); // as found
-            (void)hipGetLastError();
-            return;
-        }
-        rewritten = true;
+        const hipGraphNode_t* nodes = nullptr;
+        size_t n_nodes = 0;
+        deps.clear();
+        if (hipStreamGetCaptureInfo_v2(stream, &st, &id, nullptr, &nodes, &n_nodes) != hipSuccess) { (void)hipGetLastError(); return false; }
+        if (st != hipStreamCaptureStatusActive) return false;
+        deps.assign((const TickNode*)nodes, (const TickNode*)nodes + n_nodes);
+        return true;
     }
-    // the launch was refused or failed: the stream's dependency set as found, nothing recorded
-    void abandon() {
-        if (rewritten) {
-            (void)hipStreamUpdateCaptureDependencies(stream, (hipGraphNode_t*)found.data(), found.size(), hipStreamSetCaptureDependencies);
-            (void)hipGetLastError();
-        }
-        if (lanes) lanes->drop();
-        release();
-    }
-    // The tick has been captured.  Overlapped: the other lane's last tick joins the frontier again.  0, or < 0 when the frontier could not
-    // be put back (the capture would no longer order later work behind both lanes).
-    int end() {
-        if (!capturing) return 0;
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        const hipGraphNode_t* deps = nullptr;
-        size_t n_deps = 0;
-        unsigned long long id_now = 0;
-        TickNode node = nullptr;
-        if (hipStreamGetCaptureInfo_v2(stream, &st, &id_now, nullptr, &deps, &n_deps) == hipSuccess && st == hipStreamCaptureStatusActive && id_now == id && n_deps == 1) node = deps[0];
-        else (void)hipGetLastError();
-        int rc = 0;
-        if (rewritten) {
-            hipGraphNode_t beside = (hipGraphNode_t)planned.beside;
-            bool ok = node && hipStreamUpdateCaptureDependencies(stream, &beside, 1, hipStreamAddCaptureDependencies) == hipSuccess;
-            if (!ok) { // put the whole frontier back by hand: the tick (whatever the stream holds now) and everything found before it
-                (void)hipGetLastError();
-                std::vector<hipGraphNode_t> all((hipGraphNode_t*)found.data(), (hipGraphNode_t*)found.data() + found.size());
-                for (size_t i = 0; i < n_deps; ++i) all.push_back(deps[i]);
-                ok = hipStreamUpdateCaptureDependencies(stream, all.data(), all.size(), hipStreamSetCaptureDependencies) == hipSuccess;
-                if (!ok) (void)hipGetLastError();
-                lanes->drop();
-                g_tick_why = TickOverlap::capture_call_failed;
-                if (!ok) rc = fail(CVGS_ERR_HIP, "captured tick: the stream's capture dependencies could not be restored");
-            } else {
-                lanes->committed(planned, node, fp);
-            }
-        } else {
-            lanes->in_order(id, found.data(), found.size(), node, fp);
-        }
-        (g_tick_why == TickOverlap::overlapped ? g_ticks_overlapped : g_ticks_in_order).fetch_add(1, std::memory_order_relaxed);
-        release();
-        return rc;
-    }
-    ~TickLaneCapture() { release(); }
-private:
-    void release() {
-        lanes = nullptr;
-        capturing = rewritten = false;
-        if (lock.owns_lock()) lock.unlock();
-    }
-    hipStream_t stream = nullptr;
-    bool capturing = false, rewritten = false;
-    unsigned long long id = 0;
-    std::unique_lock<std::mutex> lock;
-    TickLanes* lanes = nullptr;
-    std::vector<TickNode> found;
-    TickFootprint fp;
-    TickLanes::Plan planned;
-};
-
-// ---- a captured tick INSIDE the launch of the tick before it (cvgs_tick_merge.h: the rule and the shape) ----------------------------------
-// The two lanes hide part of a launch's fixed cost; a tick that joins the previous tick's kernel node pays none.  Ticks of at least
-// kTickMergeMinPixels take this path INSTEAD of the lanes: merged, or in order as a node of their own that the next tick may join (a merged
-// node is a large tick, and large ticks gain nothing side by side: kTickOverlapMaxPixels).  Smaller ticks, CVGS_TICK_MERGE=0, and every tick
-// the lanes would not admit either keep the lane code above, untouched.
-std::atomic<uint64_t> g_ticks_merged{0};
-thread_local TickMerge g_merge_why = TickMerge::first_tick;
-thread_local int g_merge_chains = 0;
-const char* const kTickNoteMerge = "tick-merge"; // g_tick_note: the tick took the merge path, g_merge_why says how it went
-
-bool tick_merge_enabled() {
-    static const bool on = [] { const char* e = getenv("CVGS_TICK_MERGE"); return e ? e[0] != '0' : true; }();
-    return on;
-}
-// Tuning / test hooks, read once: CVGS_TICK_MERGE_MIN_PIXELS moves the size floor (the suite's ticks are a few hundred pixels),
-// CVGS_TICK_MERGE_MAX_CHAINS lowers the cap (the 64-against-128 sweep); neither can raise the cap beyond the argument block's 128 segments.
-int64_t tick_merge_min_pixels() {
-    static const int64_t v = [] { const char* e = getenv("CVGS_TICK_MERGE_MIN_PIXELS"); return e && *e ? (int64_t)atoll(e) : kTickMergeMinPixels; }();
-    return v;
-}
-int tick_merge_max_chains() {
-    static const int v = [] {
-        const char* e = getenv("CVGS_TICK_MERGE_MAX_CHAINS");
-        const int n = e && *e ? atoi(e) : kTickMergeMaxChains;
-        return n < 2 ? 2 : (n > kTickMergeMaxChains ? kTickMergeMaxChains : n);
-    }();
-    return v;
-}
-
-struct TickMergeCapture {
-    enum { not_taken = 0, merged = 1, in_order = 2 };
-    // not_taken: the lanes decide, as ever.  merged: the tick rides in the previous tick's node, nothing is left to launch.  in_order: launch
-    // the tick as it is, then opened() (or abandon()).  Never fails: a refused graph call leaves the node as it was and the tick in order.
-    int begin(const cvgs_chain_desc* chains, int n, const TickPlan& plan, const LaunchCtx& ctx, const ChainArgs& c, const ManySeg* segs, hipStream_t s) {
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        const hipGraphNode_t* deps = nullptr;
-        size_t n_deps = 0;
-        hipGraph_t graph = nullptr;
-        if (hipStreamGetCaptureInfo_v2(s, &st, &id, &graph, &deps, &n_deps) != hipSuccess) { (void)hipGetLastError(); return not_taken; }
-        if (st != hipStreamCaptureStatusActive) return not_taken;
-        lock = many_pool().lanes_lock();
-        state = &many_pool().captured(s);
-        // the lane rule's own admission (TickLaneCapture::begin), and the size floor
-        const bool admitted = plan.family == TickFamily::k1 && plan.carrier == TickCarrier::device_tables && !ctx.done_word && !ctx.stop_event && ctx.mirrors.n == 0 && !c.write.data2;
-        if (state->route(tick_merge_enabled(), admitted, (int64_t)plan.total_planes * c.read.dst_w * c.read.dst_h, tick_merge_min_pixels()) == TickPath::lanes) {
-            release();
-            return not_taken;
-        }
-        // what the tick would launch: the launch site builds its arguments and enqueues nothing
-        if (!mine) mine.reset(new TickLaunchRecord());
-        LaunchCtx probe(s);
-        probe.segs = segs;
-        probe.n_segs = n;
-        probe.record = mine.get();
-        probe.record_only = true;
-        const bool built = launch_k1(c, nullptr, 0, probe, false, nullptr) == 1 && mine->fn && mine->arg_ptrs;
-        tick_footprint(chains, n, segs, fp);
-        if (!built) fp.unstated(); // (a launch site that keeps no record: a node nothing joins)
-        key_of(*mine, key);
-        tick.fn = built ? mine->fn : nullptr;
-        tick.key = key.data();
-        tick.key_bytes = key.size();
-        tick.chains = n;
-        tick.max_batch = plan.max_batch;
-        tick.fp = &fp;
-        const TickNode* found = (const TickNode*)deps;
-        g_merge_why = state->merge.plan(id, found, n_deps, tick, tick_merge_max_chains());
-        if (g_merge_why == TickMerge::merged && many_pool().lanes_on_other_streams(s, id)) g_merge_why = TickMerge::other_streams;
-        if (g_merge_why == TickMerge::merged && !(state->launch && rewrite(*state->launch, (hipGraphNode_t)state->merge.node(), segs, n, plan.max_batch)))
-            g_merge_why = TickMerge::graph_call_failed;
-        if (g_merge_why != TickMerge::merged) return in_order;
-        state->merge.merged(tick);
-        g_merge_chains = state->merge.chains();
-        g_ticks_merged.fetch_add(1, std::memory_order_relaxed);
-        release();
-        return merged;
-    }
-    // the tick has been captured in order: its node (the stream's dependency set names it) is the one the next tick may join
-    void opened(hipStream_t s) {
-        if (!state) return;
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        const hipGraphNode_t* deps = nullptr;
-        size_t n_deps = 0;
-        unsigned long long id_now = 0;
-        TickNode node = nullptr;
-        if (hipStreamGetCaptureInfo_v2(s, &st, &id_now, nullptr, &deps, &n_deps) == hipSuccess && st == hipStreamCaptureStatusActive && id_now == id && n_deps == 1) node = deps[0];
-        else (void)hipGetLastError();
-        state->merge.opened(id, node, tick);
-        state->launch.swap(mine); // the launch just captured is the record's (built by the dry run from the same arguments)
-        g_ticks_in_order.fetch_add(1, std::memory_order_relaxed);
-        release();
-    }
-    void abandon() {
-        if (state) state->merge.drop();
-        release();
-    }
-    ~TickMergeCapture() { release(); }
-private:
-    // every tick of a node shares these bytes: the chain arguments without what each segment carries, and the geometry likewise
-    static void key_of(const TickLaunchRecord& r, std::vector<unsigned char>& out) {
-        ChainArgs c = r.a.c;
-        c.read.batch = c.read.used = 0;
-        c.read.table = nullptr;
-        c.write.data = nullptr;
-        out.resize(sizeof(ChainArgs) + TickLaunchRecord::kGeomBytes + 3 * sizeof(unsigned));
-        std::memcpy(out.data(), &c, sizeof(ChainArgs));
-        std::memcpy(out.data() + sizeof(ChainArgs), r.geom_key, TickLaunchRecord::kGeomBytes);
-        const unsigned shape[3] = {r.grid[0], r.block, (unsigned)r.geom_bytes}; // (grid y and z are what merging changes)
-        std::memcpy(out.data() + sizeof(ChainArgs) + TickLaunchRecord::kGeomBytes, shape, sizeof(shape));
-    }
+    bool set_deps(const TickNode* nodes, size_t n_nodes) { return update(nodes, n_nodes, hipStreamSetCaptureDependencies); }
+    bool add_deps(const TickNode* nodes, size_t n_nodes) { return update(nodes, n_nodes, hipStreamAddCaptureDependencies); }
     // The node's launch with the tick's segments behind its own: a copy is changed, the node rewritten from the copy, and the copy kept only
     // when the runtime took it.  Pointers the runtime hands back (hipGraphKernelNodeGetParams) are never used.
-    static bool rewrite(TickLaunchRecord& rec, hipGraphNode_t node, const ManySeg* segs, int n, int max_batch) {
+    bool rewrite_node(TickNode node, TickLaunchRecord& rec) {
         const int have = (int)rec.grid[2];
         if (!node || !rec.fn || !rec.arg_ptrs || have < 1 || have + n > CVGS_MAX_CHAINS) return false;
         static thread_local std::unique_ptr<TickLaunchRecord> next;
@@ -1657,45 +1453,33 @@ private:
         p.func = const_cast<void*>(next->fn);
         p.gridDim = dim3(next->grid[0], next->grid[1], next->grid[2]);
         p.blockDim = dim3(next->block);
-        p.sharedMemBytes = 0;
         p.kernelParams = args; // (copied by the call)
-        p.extra = nullptr;
-        if (hipGraphKernelNodeSetParams(node, &p) != hipSuccess) {
+        if (hipGraphKernelNodeSetParams((hipGraphNode_t)node, &p) != hipSuccess) {
             (void)hipGetLastError();
             return false;
         }
         rec = *next;
         return true;
     }
-    void release() {
-        state = nullptr;
-        if (lock.owns_lock()) lock.unlock();
+private:
+    bool update(const TickNode* nodes, size_t n_nodes, unsigned flags) {
+        if (hipStreamUpdateCaptureDependencies(stream, (hipGraphNode_t*)nodes, n_nodes, flags) == hipSuccess) return true;
+        (void)hipGetLastError();
+        return false;
     }
-    unsigned long long id = 0;
-    std::unique_lock<std::mutex> lock;
-    ManyPool::TickCaptured* state = nullptr;
-    std::unique_ptr<TickLaunchRecord> mine;
-    std::vector<unsigned char> key;
-    TickFootprint fp;
-    TickMergeTick tick;
 };
 
-// cvgs_last_error() after a successful cvgs_execute_many: the call's note and the process-wide counters
-void tick_note_text(std::string& out) {
-    char counts[96];
-    std::snprintf(counts, sizeof(counts), " [captured ticks: %llu overlapped, %llu in order]", (unsigned long long)g_ticks_overlapped.load(),
-                  (unsigned long long)g_ticks_in_order.load());
-    if (g_tick_note == kTickNoteMerge) { // the merge path: its own words, and the third counter in front of the two
-        char text[160];
-        if (g_merge_why == TickMerge::merged) std::snprintf(text, sizeof(text), "tick: %s (%d chains)", tick_merge_text(g_merge_why), g_merge_chains);
-        else std::snprintf(text, sizeof(text), "tick: %s", tick_merge_text(g_merge_why));
-        char merged[64];
-        std::snprintf(merged, sizeof(merged), " [merged ticks: %llu]", (unsigned long long)g_ticks_merged.load());
-        out = std::string(text) + merged + counts;
-        return;
-    }
-    out = g_tick_note == kTickNoteOverlap ? std::string("tick: ") + tick_overlap_text(g_tick_why) : std::string(g_tick_note);
-    out += counts;
+// every tick of a node shares these bytes: the chain arguments without what each segment carries, and the geometry likewise
+void key_of(const TickLaunchRecord& r, std::vector<unsigned char>& out) {
+    ChainArgs c = r.a.c;
+    c.read.batch = c.read.used = 0;
+    c.read.table = nullptr;
+    c.write.data = nullptr;
+    out.resize(sizeof(ChainArgs) + TickLaunchRecord::kGeomBytes + 3 * sizeof(unsigned));
+    std::memcpy(out.data(), &c, sizeof(ChainArgs));
+    std::memcpy(out.data() + sizeof(ChainArgs), r.geom_key, TickLaunchRecord::kGeomBytes);
+    const unsigned shape[3] = {r.grid[0], r.block, (unsigned)r.geom_bytes}; // (grid y and z are what merging changes)
+    std::memcpy(out.data() + sizeof(ChainArgs) + TickLaunchRecord::kGeomBytes, shape, sizeof(shape));
 }
 
 // The planned tick: 1 launched / 0 not a fused launch after all (nothing was enqueued, and `table` has given back what it took) / < 0 error.
@@ -1733,28 +1517,37 @@ int launch_tick(const cvgs_chain_desc* chains, int32_t n, const TickPlan& plan, 
     if (table.n_planes() > cvgs::kManyInlineLarge) return fail(CVGS_ERR_INVALID, "inline tick: more planes than counted");
     c.read.table = plan.carrier == TickCarrier::kernarg ? nullptr : segs[0].table; // non-null: the table variants; null + segments: planes in the arguments
     // on a capturing stream: inside the previous tick's launch, or beside the ticks before it, when that is proven safe -- else exactly as ever
-    TickMergeCapture merge;
-    const int merging = k4 ? TickMergeCapture::not_taken : merge.begin(chains, n, plan, ctx, c, segs, stream);
-    if (merging == TickMergeCapture::merged) {
-        table.finish(true, &ctx);
-        g_tick_note = kTickNoteMerge;
-        return 1;
+    const bool admitted = plan.family == TickFamily::k1 && plan.carrier == TickCarrier::device_tables && !ctx.done_word && !ctx.stop_event && ctx.mirrors.n == 0 && !c.write.data2;
+    const TickFacts facts{!k4, admitted, (int64_t)plan.total_planes * c.read.dst_w * c.read.dst_h, n, plan.max_batch};
+    HipTickStream capturing{stream, segs, n, plan.max_batch};
+    TickCapture<HipTickStream, ManyPool, hipStream_t> capture(capturing, many_pool(), stream, g_tick_note);
+    // tuning / test hooks, read once: CVGS_TICK_MERGE_MIN_PIXELS moves the size floor (the suite's ticks are a few hundred pixels),
+    // CVGS_TICK_MERGE_MAX_CHAINS lowers the cap (the 64-against-128 sweep) and cannot raise it beyond the argument block's 128 segments
+    static const TickCaptureConfig cfg{env_flag("CVGS_TICK_OVERLAP"), env_flag("CVGS_TICK_MERGE"), env_int("CVGS_TICK_MERGE_MIN_PIXELS", kTickMergeMinPixels),
+                                       (int)std::min<int64_t>(std::max<int64_t>(env_int("CVGS_TICK_MERGE_MAX_CHAINS", kTickMergeMaxChains), 2), kTickMergeMaxChains),
+                                       kTickOverlapMaxPixels};
+    const TickBegin how = capture.begin(
+        facts, cfg, [&](TickFootprint& fp) { tick_footprint(chains, n, segs, fp); },
+        [&](TickLaunchRecord& rec, std::vector<unsigned char>& key) -> const void* { // what the tick would launch: the launch site builds its arguments and enqueues nothing
+            LaunchCtx probe(stream);
+            probe.segs = segs;
+            probe.n_segs = n;
+            probe.record = &rec;
+            probe.record_only = true;
+            const bool built = launch_k1(c, nullptr, 0, probe, false, nullptr) == 1 && rec.fn && rec.arg_ptrs;
+            key_of(rec, key);
+            return built ? rec.fn : nullptr;
+        });
+    if (how != TickBegin::merged) {
+        rc = k4 ? launch_yuv_resize(c, table.planes(), table.n_planes(), 1 << 30, ctx, false, nullptr) : launch_k1(c, table.planes(), table.n_planes(), ctx, false, nullptr);
+        if (rc != 1) {
+            capture.abandon();
+            return fail(CVGS_ERR_HIP, "fused kernel launch failed");
+        }
     }
-    TickLaneCapture lane;
-    if (merging == TickMergeCapture::not_taken) lane.begin(chains, n, plan, ctx, c, segs, stream);
-    rc = k4 ? launch_yuv_resize(c, table.planes(), table.n_planes(), 1 << 30, ctx, false, nullptr) : launch_k1(c, table.planes(), table.n_planes(), ctx, false, nullptr);
-    if (rc != 1) {
-        lane.abandon();
-        merge.abandon();
-        return fail(CVGS_ERR_HIP, "fused kernel launch failed");
-    }
-    rc = 0;
-    if (merging == TickMergeCapture::in_order) merge.opened(stream);
-    else rc = lane.end();
+    const char* lost = how == TickBegin::merged ? nullptr : capture.launched();
     table.finish(true, &ctx);
-    if (rc) return rc;
-    g_tick_note = merging == TickMergeCapture::in_order ? kTickNoteMerge : kTickNoteOverlap;
-    return 1;
+    return lost ? fail(CVGS_ERR_HIP, lost) : 1;
 }
 
 int execute_many(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream) {
@@ -1770,7 +1563,8 @@ int execute_many(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream) {
         rc = dispatch(&chains[i], L, stream, false, nullptr);
         if (rc) return rc;
     }
-    g_tick_note = plan.why ? plan.why : "not fused: the tick kernel does not take these chains"; // (an un-fused tick is not silent)
+    g_tick_note = TickNote();
+    g_tick_note.plain = plan.why ? plan.why : "not fused: the tick kernel does not take these chains"; // (an un-fused tick is not silent)
     return CVGS_OK;
 }
 
@@ -1955,8 +1749,8 @@ int cvgs_abi_version(void) { return CVGS_ABI_VERSION; }
 const char* cvgs_version_string(void) { return "cvgs-hip 0.2 (gfx950)"; }
 const char* cvgs_last_error(void) {
     if (g_tick_note) { // a successful cvgs_execute_many left a note: how its tick was launched
-        tick_note_text(g_err);
-        g_tick_note = nullptr;
+        g_err = tick_note_text(g_tick_note);
+        g_tick_note = TickNote();
     }
     return g_err.c_str();
 }

@@ -1,8 +1,8 @@
 // cvgs_tick_merge.h -- may a fused K1 tick captured on a stream ride in the LAUNCH of the tick captured before it?
-// Pure host logic (no HIP header), beside cvgs_tick_overlap.h whose footprints and node handles it uses: cvgs_api.cpp feeds it what the tick
-// would launch (function, the comparable bytes of its argument block, chain count, largest batch, footprint) and the capture's dependency
-// set, and rewrites the previous tick's graph node when the answer is `merged`; tests/cpp/tick_merge_model.cpp holds it to a byte-set model
-// without a GPU.
+// Pure host logic (no HIP header), beside cvgs_tick_overlap.h whose footprints and node handles it uses: the driver in cvgs_tick_capture.h
+// feeds it what the tick would launch (function, the comparable bytes of its argument block, chain count, largest batch, footprint) and the
+// capture's dependency set, and has cvgs_api.cpp rewrite the previous tick's graph node when the answer is `merged`;
+// tests/cpp/tick_merge_model.cpp holds it to a byte-set model without a GPU.
 //
 // THE SHAPE: one kernel node takes consecutive ticks until it is full.  The K1 tick kernel reads its chain from seg[blockIdx.z] and leaves
 // early on a crop index beyond the chain's batch, so a tick joins a node by appending its segments (call order), growing gridDim.z by its
@@ -20,7 +20,7 @@ namespace cvgs {
 // tie within the run-to-run spread (profiles/tick_merge_abab.txt: 2.306 us per frame both), so the cap is the block's: fewest launches.
 constexpr int kTickMergeMaxChains = 128;
 // The smallest tick (output pixels: planes x width x height) that is merged at all; smaller ticks keep the two-lane capture of
-// cvgs_tick_overlap.h unchanged.  Swept over ticks of 2, 4 and 16 frames of 50 crops to 64 x 128 (a tick of one chain is not a fused tick):
+// cvgs_tick_overlap.h unchanged (its own size limit, kTickOverlapMaxPixels, stands beside the driver in cvgs_tick_capture.h).  Swept over ticks of 2, 4 and 16 frames of 50 crops to 64 x 128 (a tick of one chain is not a fused tick):
 // merging won at every size (3.62 -> 2.53, 2.65 -> 2.30, 2.39 -> 2.30 us per frame), so the floor is the smallest size swept.
 constexpr int64_t kTickMergeMinPixels = 100ll * 64 * 128;
 

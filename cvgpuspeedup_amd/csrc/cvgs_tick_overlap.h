@@ -1,7 +1,7 @@
 // cvgs_tick_overlap.h -- may a fused tick captured on a stream run BESIDE the ticks captured before it, and behind which graph nodes?
-// Pure host logic (no HIP header, no allocation policy of its own): cvgs_api.cpp feeds it the byte ranges a tick reads and writes and the
-// capture's dependency sets as opaque node handles, and does what the answer says; tests/cpp/tick_overlap_model.cpp holds it to a byte-set
-// model and to an ordering model without a GPU.
+// Pure host logic (no HIP header, no allocation policy of its own): the driver in cvgs_tick_capture.h feeds it the byte ranges a tick reads
+// and writes and the capture's dependency sets as opaque node handles, and does what the answer says; tests/cpp/tick_overlap_model.cpp holds
+// it to a byte-set model and to an ordering model without a GPU.
 //
 // THE SHAPE: two lanes, never more.  Consecutive overlappable ticks A B C D ... alternate between two chains of graph nodes: B is captured
 // behind what stood in front of A (P), C behind A only, D behind B only.  The stream's frontier always holds both lanes' last ticks, so

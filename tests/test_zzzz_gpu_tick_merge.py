@@ -48,6 +48,13 @@ DIFFERENT = "not merged: another kernel, program, target shape or geometry"
 NO_HULL = "not merged: no hull stated"
 FULL = "not merged: the previous launch is full"
 CAP = 128
+# A K4 (NV12) tick of 2 chains between two K1 ticks, one capture: each note up to the counters, three kernel nodes in a line.  Recorded from
+# the commit before the capture driver moved into cvgs_tick_capture.h (the K4 tick takes the lane code and is never shown to the merge rule,
+# whose node therefore stands: the K1 tick behind it finds a foreign node, not a first tick).
+K4_BETWEEN = ["tick: in order, not merged: no earlier tick of this capture on the stream [merged ticks: ",
+              "tick: in order: not a K1 tick over device tables, or pooled state rides on the launch [captured ticks: ",
+              "tick: in order, not merged: something else was captured since the previous tick [merged ticks: "]
+K4_BETWEEN_NODES = 3
 
 
 def _chain(src, crops, out, dst, table=None, alpha=W.K1_ALPHA):
@@ -121,6 +128,35 @@ class Tick:
         for m, b in enumerate(self.bufs):
             bands = b.cpu().numpy()
             assert (bands[:GUARD] == FILL).all() and (bands[-GUARD:] == FILL).all(), "%s: chain %d wrote into a guard band" % (what, m)
+
+
+class Nv12Tick(Tick):
+    """A K4 tick: two chains (3 crops, 1 crop) of one 96 x 64 NV12 surface each, host descriptors in the kernel arguments."""
+    RECTS = [[(0, 0, 96, 64), (10, 8, 40, 48), (32, 16, 32, 32)], [(2, 2, 64, 60)]]
+
+    def __init__(self, dev, seed, dst=(8, 16)):
+        import torch
+        self.dst, self.plane = dst, 3 * dst[0] * dst[1]
+        self.surfs = [H.random_u8((FH * 3 // 2, FW), seed=seed + m) for m in range(2)]
+        self.st = [torch.from_numpy(s).to(dev) for s in self.surfs]
+        self.bufs = [torch.full((2 * GUARD + len(self.RECTS[m]) * self.plane,), FILL, dtype=torch.float32, device=dev) for m in range(2)]
+        self.outs = [b[GUARD:GUARD + len(self.RECTS[m]) * self.plane].view(len(self.RECTS[m]), self.plane) for m, b in enumerate(self.bufs)]
+        self.low = [cvgs.lower(self._ops(cvgs.GpuMat.from_tensor(self.st[m], cvgs.CV_8UC1), m, cvgs.GpuMat.from_tensor(self.outs[m], cvgs.CV_32FC1))) for m in range(2)]
+        self.arr = cvgs.pack_chains(self.low)
+
+    def _ops(self, surf, m, out):
+        f = cvgs.make_type(cvgs.CV_32F, 3)
+        luma = cvgs.GpuMat(FH, FW, cvgs.CV_8UC1, surf.data, surf.step, owner=surf.owner)
+        return [cvgs.read_nv12([luma.nv12_roi(*r) for r in self.RECTS[m]], self.dst, capi.YUV_FULL, capi.BT601, False), cvgs.cvtColor(cvgs.COLOR_RGB2BGR, f),
+                cvgs.multiply(f, [W.K1_ALPHA] * 3), cvgs.subtract(f, W.K1_SUB[3]), cvgs.divide(f, W.K1_DIV[3]), cvgs.split(f, out, self.dst)]
+
+    def refs(self, oracle):
+        res = []
+        for m in range(2):
+            ref = np.full((len(self.RECTS[m]), self.plane), FILL, np.float32)
+            oracle.execute(cvgs.lower(self._ops(cvgs.GpuMat.from_array(self.surfs[m], cvgs.CV_8UC1), m, cvgs.GpuMat.from_array(ref, cvgs.CV_32FC1))))
+            res.append(ref)
+        return res
 
 
 def grid_of(node):
@@ -275,6 +311,23 @@ def _scenarios(lib, dev, oracle):
     two.destroy()
     yield "two_captures", f
 
+    # ---- a K4 tick between two K1 ticks: in order through the lane code, and the merge rule's node stands --------------------------------
+    nv = Nv12Tick(dev, 8600)
+    nv_refs = nv.refs(oracle)
+    with T.gpu_step():
+        nv_eager, = _eager(lib, [nv])
+    for t in ticks[:2]:
+        t.refill()
+    cap = captured([ticks[0], nv, ticks[1]])
+    f = facts(cap)
+    assert f["kernels"] == K4_BETWEEN_NODES == f["nodes"] and f["new_nodes"] == [1, 1, 1] and f["linear"], f
+    assert all(note.startswith(want) for note, want in zip(cap.notes, K4_BETWEEN)) and len(cap.notes) == len(K4_BETWEEN), cap.notes
+    for k in range(2):
+        ticks[k].check(refs[k], "a K4 tick between, K1 tick %d" % k, eager[k])
+    nv.check(nv_refs, "a K4 tick between, the K4 tick", nv_eager)
+    cap.destroy()
+    yield "k4_between", f
+
 
 def _switched_off(lib, dev, oracle):
     """CVGS_TICK_MERGE=0: the graph of the lane rule -- four nodes in two lanes, the lane notes, no merged-tick counter."""
@@ -352,6 +405,12 @@ def test_a_full_node_is_followed_by_a_second_one(merged):
 def test_two_captures_in_a_row_share_no_state(merged):
     f = _scenario(merged, "two_captures")
     assert f["kernels"] == 1 and FIRST in f["notes"][0] and MERGED in f["notes"][1], f
+
+
+def test_a_k4_tick_between_two_k1_ticks_leaves_the_merge_rule_alone(merged):
+    f = _scenario(merged, "k4_between")
+    assert f["kernels"] == K4_BETWEEN_NODES and f["linear"], f
+    assert [n[:len(w)] for n, w in zip(f["notes"], K4_BETWEEN)] == K4_BETWEEN, f["notes"]
 
 
 def test_every_scenario_ran(merged):

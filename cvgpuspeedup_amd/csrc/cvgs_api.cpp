@@ -1302,13 +1302,15 @@ bool chains_independent(const cvgs_chain_desc* const* chains, int n) {
     return true;
 }
 
-// A TICK: n chains of one shape in ONE launch.  Three kernel families take one:
+// A TICK: n chains of one shape in ONE launch.  Four kernel families take one:
 //   pointwise  per-pixel reads of u8 planes of ONE size, host descriptors, a dense fp32 target per chain (round 6; the reference's batched per-pixel
 //              chains, tests/batchread/test_batchread_x_write3D.cu:92-96: BATCH crops -> convertTo -> subtract -> divide -> tensor, launch-bound
 //              at 4 us for 50 crops of 60 x 120)
 //   k1, k4     a resize of pixels (K1) or of decoder surfaces (K4) into a planar tensor
+//   area       the INTER_AREA resize of u8 C3 / C4 pixels into a planar fp32 / fp16 / bf16 tensor (k_area.hip: every chain try_area_fast takes), with
+//              K1's three carriers -- device tables included; a captured AREA tick is one kernel node in stream order (overlap and merge stay K1's)
 // plan_tick answers from the descriptors alone; what only the LOWERED chains show is found by launch_tick, which then gives up before anything is enqueued.
-enum class TickFamily { none, pointwise, k1, k4 };
+enum class TickFamily { none, pointwise, k1, k4, area };
 struct TickPlan {
     TickFamily family = TickFamily::none;
     TickCarrier carrier = TickCarrier::kernarg;
@@ -1329,11 +1331,12 @@ TickPlan plan_tick(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream)
     TickPlan plan;
     plan.family = c0.read.kind == CVGS_READ_PIXEL ? TickFamily::pointwise
                 : c0.read.kind == CVGS_READ_RESIZE_LINEAR ? TickFamily::k1
-                : c0.read.kind == CVGS_READ_NV12_RESIZE_LINEAR ? TickFamily::k4 : TickFamily::none;
+                : c0.read.kind == CVGS_READ_NV12_RESIZE_LINEAR ? TickFamily::k4
+                : c0.read.kind == CVGS_READ_RESIZE_AREA ? TickFamily::area : TickFamily::none;
     if (plan.family == TickFamily::none) return refused("not fused: no tick kernel for this read kind");
     const bool pw = plan.family == TickFamily::pointwise;
     const bool tables = (c0.read.flags & CVGS_READ_FLAG_TABLE_ON_DEVICE) != 0;
-    if (tables && plan.family != TickFamily::k1) return refused("not fused: device tables outside K1"); // per-pixel reads and K4's per-plane preconditions want the planes on the host
+    if (tables && plan.family != TickFamily::k1 && plan.family != TickFamily::area) return refused("not fused: device tables outside K1 and AREA"); // per-pixel reads and K4's per-plane preconditions want the planes on the host
     int min_batch = 1;
     const cvgs_chain_desc* ptrs[CVGS_MAX_CHAINS];
     for (int i = 0; i < n; ++i) { // one shape (same_shape: kind, program, target extent), one descriptor form; the planes counted
@@ -1348,10 +1351,10 @@ TickPlan plan_tick(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream)
         min_batch = std::min(min_batch, (int)c.read.batch);
         ptrs[i] = &c;
     }
-    // host-described K1 chains of u8 pixels with 3 / 4 channels, K4 chains of interleaved chroma / packed 4:2:2 / planar 4:4:4, pointwise chains:
+    // host-described K1 and AREA chains of u8 pixels with 3 / 4 channels, K4 chains of interleaved chroma / packed 4:2:2 / planar 4:4:4, pointwise chains:
     // at most kManyInlineLarge planes in all travel in the kernel arguments (cvgs_device.h: KernArgsManyInline)
     static const bool inline_ok = env_flag("CVGS_MANY_INLINE");
-    const bool k1_u8 = plan.family == TickFamily::k1 && CVGS_TYPE_CN(c0.read.src_type) >= 3 && CVGS_TYPE_DEPTH(c0.read.src_type) == CVGS_DEPTH_8U;
+    const bool k1_u8 = (plan.family == TickFamily::k1 || plan.family == TickFamily::area) && CVGS_TYPE_CN(c0.read.src_type) >= 3 && CVGS_TYPE_DEPTH(c0.read.src_type) == CVGS_DEPTH_8U;
     const bool k4_il = plan.family == TickFamily::k4 &&
                        (c0.read.yuv_layout == CVGS_YUV_NV12 || c0.read.yuv_layout == CVGS_YUV_NV21 || c0.read.yuv_layout == CVGS_YUV_P010 ||
                         is_yuv422(c0.read.yuv_layout) || is_yuv444(c0.read.yuv_layout));
@@ -1378,6 +1381,7 @@ bool tick_kernel_takes(TickFamily family, const Lowered& L0, hipStream_t stream)
     pctx.segs = &one;
     pctx.n_segs = 1;
     if (family == TickFamily::k4) return launch_yuv_resize(probe, nullptr, 0, 1 << 30, pctx, true, nullptr) == 1; // K4 checks its planes on the host
+    if (family == TickFamily::area) return !L0.uses_64f && launch_area_many(probe, nullptr, 0, pctx, true, nullptr) == 1; // (CV_64F values: dispatch's refusal, chain by chain)
     return launch_k1(probe, nullptr, 0, pctx, true, nullptr) == 1;
 }
 // Can lowered chain L ride in the family's tick with chain 0 (L0)?
@@ -1484,7 +1488,7 @@ void key_of(const TickLaunchRecord& r, std::vector<unsigned char>& out) {
 
 // The planned tick: 1 launched / 0 not a fused launch after all (nothing was enqueued, and `table` has given back what it took) / < 0 error.
 int launch_tick(const cvgs_chain_desc* chains, int32_t n, const TickPlan& plan, hipStream_t stream) {
-    const bool pw = plan.family == TickFamily::pointwise, k4 = plan.family == TickFamily::k4;
+    const bool pw = plan.family == TickFamily::pointwise, k4 = plan.family == TickFamily::k4, area = plan.family == TickFamily::area;
     ManySeg segs[CVGS_MAX_CHAINS];
     TickTable table;
     Lowered L0; // the shared read / program / write arguments come from chain 0
@@ -1539,7 +1543,8 @@ int launch_tick(const cvgs_chain_desc* chains, int32_t n, const TickPlan& plan, 
             return built ? rec.fn : nullptr;
         });
     if (how != TickBegin::merged) {
-        rc = k4 ? launch_yuv_resize(c, table.planes(), table.n_planes(), 1 << 30, ctx, false, nullptr) : launch_k1(c, table.planes(), table.n_planes(), ctx, false, nullptr);
+        rc = k4 ? launch_yuv_resize(c, table.planes(), table.n_planes(), 1 << 30, ctx, false, nullptr)
+           : area ? launch_area_many(c, table.planes(), table.n_planes(), ctx, false, nullptr) : launch_k1(c, table.planes(), table.n_planes(), ctx, false, nullptr);
         if (rc != 1) {
             capture.abandon();
             return fail(CVGS_ERR_HIP, "fused kernel launch failed");

@@ -283,6 +283,11 @@ int launch_warp(const ChainArgs& c, const WarpPlane* planes, int n, const WarpPl
 // INTER_AREA resize (k_area.hip): CVGS_READ_RESIZE_AREA chains, planes as for the bilinear resize (inline up to CVGS_KERNARG_PLANES,
 // else c.read.table).  The fast kernels (u8 C3/C4 -> static program -> planar fp32 / fp16 / bf16 tensor) or the interpreted one; 0 or a HIP error code
 int launch_area(const ChainArgs& c, const PlaneParams* inline_planes, int n_inline, uint32_t chain_flags, void* stream, bool dry_run, LaunchInfo* info);
+// The fast AREA kernel for the chains of a cvgs_execute_many launch (ctx.segs; c.read.batch is the largest batch), with launch_k1's carriers:
+// c.read.table != nullptr: every segment's table is a device address (the callers' tables, or the staged host table with ctx.done_word /
+// ctx.stop_event); nullptr: `planes` holds the planes of all chains (at most kManyInlineLarge) and travels in the kernel arguments.
+// 1 launched (dry run: would launch) / 0 not a chain the fast kernel takes / < 0 error
+int launch_area_many(const ChainArgs& c, const PlaneParams* planes, int n_planes, LaunchCtx& ctx, bool dry_run, LaunchInfo* info);
 
 // INTER_AREA resize of 4:2:0 decoder surfaces (k_yuv_area.hip): CVGS_READ_NV12_RESIZE_AREA chains over NV12 / NV21 / P010 views, planes as for
 // the bilinear NV12 resize.  The fast kernels (8-bit NV12 / NV21 -> static program -> planar fp32 / fp16 / bf16 tensor) or the interpreted one;

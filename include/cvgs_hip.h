@@ -154,8 +154,13 @@ typedef enum cvgs_read_kind {
      *     16S, 16F, 16BF; 32F as it is; 32S converted).
      * Outside the window: background; planes z >= used_planes: the default value, then the chain's program -- as for the bilinear kind.
      * A view shrunk by exactly 2 on both axes gives the exact mean of each 2 x 2 block; a view as large as its target reproduces it.
-     * Served by cvgs_execute, and one by one by cvgs_execute_many.  CVGS_ERR_UNSUPPORTED: CV_64F sources or values, mirrors, the
-     * descriptor queue, cvgs_circular_update.  Decoder surfaces have an AREA kind of their own, CVGS_READ_NV12_RESIZE_AREA below.       */
+     * Served by cvgs_execute and by cvgs_execute_many.  cvgs_execute_many fuses independent chains of one shape into ONE launch when
+     * they are the fast kernel's: 8U sources of 3 / 4 channels, a program without casts (but a trailing cast to 16F / 16BF), a planar
+     * CVGS_WRITE_TENSOR_SPLIT / _T_SPLIT target of 32F / 16F / 16BF -- over host descriptors or device plane tables (stated hull or
+     * vouched), bit-identical to one cvgs_execute per chain; a captured AREA tick is one kernel node in stream order.  Every other AREA
+     * chain (other depths or channel counts, packed or per-plane targets, CVGS_CHAIN_FORCE_GENERIC, differing shapes, dependent chains)
+     * runs one by one, in order, and cvgs_last_error() says why ("not fused: ...").  CVGS_ERR_UNSUPPORTED: CV_64F sources or values, mirrors,
+     * the descriptor queue, cvgs_circular_update.  Decoder surfaces have an AREA kind of their own, CVGS_READ_NV12_RESIZE_AREA below.    */
     CVGS_READ_RESIZE_AREA = 6,
     /* 7: reserved (CVGS_ERR_INVALID) */
     /* INTER_AREA (box filter) resize of 4:2:0 DECODER SURFACES: an ENGINE EXTENSION.  For surfaces and crops that shrink by large factors
@@ -436,10 +441,11 @@ int cvgs_execute(const cvgs_chain_desc* chain, cvgs_stream_t stream);
  * a serving loop with several cameras amortises that floor by submitting its frames together.  Chains whose read is
  * a bilinear resize of 8U/16U/16S/32F pixels, or of NV12 / NV21 surfaces or crops of them (host descriptors), into a planar
  * fp32 / fp16 tensor (the K1 / K4 shapes) -- or, since round 6, a per-pixel read of 8U planes of ONE size (host descriptors) through an fp32 program into a
- * dense fp32 tensor / packed pixels (the reference's batched pointwise chains, tests/batchread/test_batchread_x_write3D.cu:92-96) --, and that agree in
+ * dense fp32 tensor / packed pixels (the reference's batched pointwise chains, tests/batchread/test_batchread_x_write3D.cu:92-96), or an INTER_AREA
+ * resize of 8U pixels with 3 / 4 channels into a planar fp32 / fp16 / bf16 tensor (CVGS_READ_RESIZE_AREA; host descriptors or device tables) --, and that agree in
  * everything except read.src / batch / used_planes and write.data / planes (same source type, target size,
  * aspect-ratio mode, background, YUV range / primaries / layout, pointwise stages and operands, write kind and type), are
- * fused into ONE launch of the K1 (or K4) kernel: grid z = chain, grid y = crop.  Results are bit-identical to n_chains separate cvgs_execute calls (same
+ * fused into ONE launch of the K1 (or K4, pointwise, AREA) kernel: grid z = chain, grid y = crop.  Results are bit-identical to n_chains separate cvgs_execute calls (same
  * kernel code; tests/test_gpu_many.py).  Any other set of chains is executed one by one, in order -- and so is a set whose
  * chains are NOT independent (two chains write overlapping bytes, or a source view of one -- chroma rows of a 4:2:0
  * surface included -- lies inside another's output: fused chains run concurrently; chains whose plane table lives on the device are checked

@@ -1278,7 +1278,7 @@ bool chains_independent(const cvgs_chain_desc* const* chains, int n) {
         }
         const cvgs_image2d* src = (const cvgs_image2d*)c.read.src;
         if (!src) continue;
-        const bool yuv = c.read.kind == CVGS_READ_NV12_RESIZE_LINEAR || c.read.kind == CVGS_READ_NV12;
+        const bool yuv = is_nv12(c.read.kind); // (the AREA kind of decoder surfaces included: its chroma rows are read like the bilinear kind's)
         const size_t px_bytes = (size_t)depth_bytes(CVGS_TYPE_DEPTH(c.read.src_type)) * (size_t)CVGS_TYPE_CN(c.read.src_type);
         const int n_src = c.read.batch < c.read.used_planes ? c.read.batch : c.read.used_planes;
         // the hull of the chain's views first (a tick's crops all lie inside one frame): only a target that meets the hull is compared view by view
@@ -1302,15 +1302,17 @@ bool chains_independent(const cvgs_chain_desc* const* chains, int n) {
     return true;
 }
 
-// A TICK: n chains of one shape in ONE launch.  Four kernel families take one:
+// A TICK: n chains of one shape in ONE launch.  Five kernel families take one:
 //   pointwise  per-pixel reads of u8 planes of ONE size, host descriptors, a dense fp32 target per chain (round 6; the reference's batched per-pixel
 //              chains, tests/batchread/test_batchread_x_write3D.cu:92-96: BATCH crops -> convertTo -> subtract -> divide -> tensor, launch-bound
 //              at 4 us for 50 crops of 60 x 120)
 //   k1, k4     a resize of pixels (K1) or of decoder surfaces (K4) into a planar tensor
 //   area       the INTER_AREA resize of u8 C3 / C4 pixels into a planar fp32 / fp16 / bf16 tensor (k_area.hip: every chain try_area_fast takes), with
 //              K1's three carriers -- device tables included; a captured AREA tick is one kernel node in stream order (overlap and merge stay K1's)
+//   yuv_area   the INTER_AREA resize of 8-bit NV12 / NV21 surfaces into a planar fp32 / fp16 / bf16 tensor (k_yuv_area.hip: every chain
+//              try_yuv_area_fast takes), with the same three carriers and the same place in a captured stream as `area`
 // plan_tick answers from the descriptors alone; what only the LOWERED chains show is found by launch_tick, which then gives up before anything is enqueued.
-enum class TickFamily { none, pointwise, k1, k4, area };
+enum class TickFamily { none, pointwise, k1, k4, area, yuv_area };
 struct TickPlan {
     TickFamily family = TickFamily::none;
     TickCarrier carrier = TickCarrier::kernarg;
@@ -1332,11 +1334,13 @@ TickPlan plan_tick(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream)
     plan.family = c0.read.kind == CVGS_READ_PIXEL ? TickFamily::pointwise
                 : c0.read.kind == CVGS_READ_RESIZE_LINEAR ? TickFamily::k1
                 : c0.read.kind == CVGS_READ_NV12_RESIZE_LINEAR ? TickFamily::k4
-                : c0.read.kind == CVGS_READ_RESIZE_AREA ? TickFamily::area : TickFamily::none;
+                : c0.read.kind == CVGS_READ_RESIZE_AREA ? TickFamily::area
+                : c0.read.kind == CVGS_READ_NV12_RESIZE_AREA ? TickFamily::yuv_area : TickFamily::none;
     if (plan.family == TickFamily::none) return refused("not fused: no tick kernel for this read kind");
     const bool pw = plan.family == TickFamily::pointwise;
     const bool tables = (c0.read.flags & CVGS_READ_FLAG_TABLE_ON_DEVICE) != 0;
-    if (tables && plan.family != TickFamily::k1 && plan.family != TickFamily::area) return refused("not fused: device tables outside K1 and AREA"); // per-pixel reads and K4's per-plane preconditions want the planes on the host
+    const bool any_area = plan.family == TickFamily::area || plan.family == TickFamily::yuv_area; // (lower() admits device tables of NV12 / NV21 only for the surface kind)
+    if (tables && plan.family != TickFamily::k1 && !any_area) return refused("not fused: device tables outside K1 and AREA"); // per-pixel reads and K4's per-plane preconditions want the planes on the host
     int min_batch = 1;
     const cvgs_chain_desc* ptrs[CVGS_MAX_CHAINS];
     for (int i = 0; i < n; ++i) { // one shape (same_shape: kind, program, target extent), one descriptor form; the planes counted
@@ -1351,15 +1355,17 @@ TickPlan plan_tick(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream)
         min_batch = std::min(min_batch, (int)c.read.batch);
         ptrs[i] = &c;
     }
-    // host-described K1 and AREA chains of u8 pixels with 3 / 4 channels, K4 chains of interleaved chroma / packed 4:2:2 / planar 4:4:4, pointwise chains:
+    // host-described K1 and AREA chains of u8 pixels with 3 / 4 channels, K4 chains of interleaved chroma / packed 4:2:2 / planar 4:4:4, AREA chains of
+    // 8-bit NV12 / NV21 surfaces, pointwise chains:
     // at most kManyInlineLarge planes in all travel in the kernel arguments (cvgs_device.h: KernArgsManyInline)
     static const bool inline_ok = env_flag("CVGS_MANY_INLINE");
     const bool k1_u8 = (plan.family == TickFamily::k1 || plan.family == TickFamily::area) && CVGS_TYPE_CN(c0.read.src_type) >= 3 && CVGS_TYPE_DEPTH(c0.read.src_type) == CVGS_DEPTH_8U;
     const bool k4_il = plan.family == TickFamily::k4 &&
                        (c0.read.yuv_layout == CVGS_YUV_NV12 || c0.read.yuv_layout == CVGS_YUV_NV21 || c0.read.yuv_layout == CVGS_YUV_P010 ||
                         is_yuv422(c0.read.yuv_layout) || is_yuv444(c0.read.yuv_layout));
+    const bool ya_il = plan.family == TickFamily::yuv_area && (c0.read.yuv_layout == CVGS_YUV_NV12 || c0.read.yuv_layout == CVGS_YUV_NV21);
     if (tables) plan.carrier = TickCarrier::device_tables;
-    else if ((pw || (inline_ok && (k1_u8 || k4_il))) && plan.total_planes <= (size_t)cvgs::kManyInlineLarge) plan.carrier = TickCarrier::kernarg;
+    else if ((pw || (inline_ok && (k1_u8 || k4_il || ya_il))) && plan.total_planes <= (size_t)cvgs::kManyInlineLarge) plan.carrier = TickCarrier::kernarg;
     else if (pw) return refused("not fused: too many planes for a pointwise tick"); // (the pointwise tick has no table form)
     else plan.carrier = TickCarrier::host_table;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -1382,6 +1388,7 @@ bool tick_kernel_takes(TickFamily family, const Lowered& L0, hipStream_t stream)
     pctx.n_segs = 1;
     if (family == TickFamily::k4) return launch_yuv_resize(probe, nullptr, 0, 1 << 30, pctx, true, nullptr) == 1; // K4 checks its planes on the host
     if (family == TickFamily::area) return !L0.uses_64f && launch_area_many(probe, nullptr, 0, pctx, true, nullptr) == 1; // (CV_64F values: dispatch's refusal, chain by chain)
+    if (family == TickFamily::yuv_area) return !L0.uses_64f && launch_yuv_area_many(probe, nullptr, 0, pctx, true, nullptr) == 1; // (no per-plane host preconditions: byte loads, odd sizes)
     return launch_k1(probe, nullptr, 0, pctx, true, nullptr) == 1;
 }
 // Can lowered chain L ride in the family's tick with chain 0 (L0)?
@@ -1488,7 +1495,7 @@ void key_of(const TickLaunchRecord& r, std::vector<unsigned char>& out) {
 
 // The planned tick: 1 launched / 0 not a fused launch after all (nothing was enqueued, and `table` has given back what it took) / < 0 error.
 int launch_tick(const cvgs_chain_desc* chains, int32_t n, const TickPlan& plan, hipStream_t stream) {
-    const bool pw = plan.family == TickFamily::pointwise, k4 = plan.family == TickFamily::k4, area = plan.family == TickFamily::area;
+    const bool pw = plan.family == TickFamily::pointwise, k4 = plan.family == TickFamily::k4, area = plan.family == TickFamily::area, yuv_area = plan.family == TickFamily::yuv_area;
     ManySeg segs[CVGS_MAX_CHAINS];
     TickTable table;
     Lowered L0; // the shared read / program / write arguments come from chain 0
@@ -1544,7 +1551,8 @@ int launch_tick(const cvgs_chain_desc* chains, int32_t n, const TickPlan& plan, 
         });
     if (how != TickBegin::merged) {
         rc = k4 ? launch_yuv_resize(c, table.planes(), table.n_planes(), 1 << 30, ctx, false, nullptr)
-           : area ? launch_area_many(c, table.planes(), table.n_planes(), ctx, false, nullptr) : launch_k1(c, table.planes(), table.n_planes(), ctx, false, nullptr);
+           : area ? launch_area_many(c, table.planes(), table.n_planes(), ctx, false, nullptr)
+           : yuv_area ? launch_yuv_area_many(c, table.planes(), table.n_planes(), ctx, false, nullptr) : launch_k1(c, table.planes(), table.n_planes(), ctx, false, nullptr);
         if (rc != 1) {
             capture.abandon();
             return fail(CVGS_ERR_HIP, "fused kernel launch failed");

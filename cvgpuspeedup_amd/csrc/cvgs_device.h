@@ -293,6 +293,9 @@ int launch_area_many(const ChainArgs& c, const PlaneParams* planes, int n_planes
 // the bilinear NV12 resize.  The fast kernels (8-bit NV12 / NV21 -> static program -> planar fp32 / fp16 / bf16 tensor) or the interpreted one;
 // 0 or a HIP error code
 int launch_yuv_area(const ChainArgs& c, const PlaneParams* inline_planes, int n_inline, uint32_t chain_flags, void* stream, bool dry_run, LaunchInfo* info);
+// The fast kernel of the above for the chains of a cvgs_execute_many launch (8-bit NV12 / NV21; ctx.segs, c.read.batch is the largest batch),
+// with launch_area_many's carriers and answers: device tables or the staged host table (c.read.table != nullptr), or `planes` in the kernel arguments
+int launch_yuv_area_many(const ChainArgs& c, const PlaneParams* planes, int n_planes, LaunchCtx& ctx, bool dry_run, LaunchInfo* info);
 
 // NV12 / NV21 encoder surfaces (k_nv12_write.hip): CVGS_WRITE_NV12 chains behind a per-pixel, bilinear or NV12 read, planes as for the
 // bilinear resize, targets in c.dst_inline / c.write.table (DstPlane::pad = the chroma offset).  The fast kernel (NV12 / NV21 surface ->

@@ -192,8 +192,15 @@ typedef enum cvgs_read_kind {
      *     default-value rules of the bilinear kind, then the chain's program.  The conversion is affine with no clamp: this equals "convert
      *     every pixel, then box-filter" in exact arithmetic and differs from it by rounding only.
      * A view as large as its target reproduces CVGS_READ_NV12's value; a view shrunk by exactly 2 converts the mean of each 2 x 2 luma block
-     * with its one chroma sample.  Served by cvgs_execute, and one by one by cvgs_execute_many.  CVGS_ERR_UNSUPPORTED, before anything is
-     * enqueued: CV_64F values, mirrors, the descriptor queue, cvgs_circular_update, CVGS_WRITE_NV12 behind it.                          */
+     * with its one chroma sample.  Served by cvgs_execute and by cvgs_execute_many.  cvgs_execute_many fuses independent chains of one
+     * shape into ONE launch when they are the fast kernel's: 8-bit NV12 / NV21 views, a program that keeps the CV_32F value and its channel
+     * count (MUL / ADD / SUB / DIV / REORDER, and a trailing cast to 16F / 16BF), a planar CVGS_WRITE_TENSOR_SPLIT / _T_SPLIT target of
+     * 32F / 16F / 16BF -- over device plane tables (stated hull or vouched), host descriptors in the kernel arguments (at most 1024 planes
+     * in all) or the staged host table, bit-identical to one cvgs_execute per chain; a captured tick of this kind is one kernel node in
+     * stream order.  Every other chain of this kind (P010, packed, u8 or per-plane targets, CVGS_CHAIN_FORCE_GENERIC, differing shapes,
+     * dependent chains -- a view's chroma rows count) runs one by one, in order, and cvgs_last_error() says why ("not fused: ...").
+     * CVGS_ERR_UNSUPPORTED, before anything is enqueued: CV_64F values, mirrors, the descriptor queue, cvgs_circular_update,
+     * CVGS_WRITE_NV12 behind it.                                                                                                          */
     CVGS_READ_NV12_RESIZE_AREA = 8
 } cvgs_read_kind;
 
@@ -442,7 +449,8 @@ int cvgs_execute(const cvgs_chain_desc* chain, cvgs_stream_t stream);
  * a bilinear resize of 8U/16U/16S/32F pixels, or of NV12 / NV21 surfaces or crops of them (host descriptors), into a planar
  * fp32 / fp16 tensor (the K1 / K4 shapes) -- or, since round 6, a per-pixel read of 8U planes of ONE size (host descriptors) through an fp32 program into a
  * dense fp32 tensor / packed pixels (the reference's batched pointwise chains, tests/batchread/test_batchread_x_write3D.cu:92-96), or an INTER_AREA
- * resize of 8U pixels with 3 / 4 channels into a planar fp32 / fp16 / bf16 tensor (CVGS_READ_RESIZE_AREA; host descriptors or device tables) --, and that agree in
+ * resize of 8U pixels with 3 / 4 channels, or of 8-bit NV12 / NV21 surfaces or crops of them, into a planar fp32 / fp16 / bf16 tensor
+ * (CVGS_READ_RESIZE_AREA, CVGS_READ_NV12_RESIZE_AREA; host descriptors or device tables) --, and that agree in
  * everything except read.src / batch / used_planes and write.data / planes (same source type, target size,
  * aspect-ratio mode, background, YUV range / primaries / layout, pointwise stages and operands, write kind and type), are
  * fused into ONE launch of the K1 (or K4, pointwise, AREA) kernel: grid z = chain, grid y = crop.  Results are bit-identical to n_chains separate cvgs_execute calls (same

@@ -134,6 +134,20 @@ class WarpTableDesc(C.Structure):
                 ("count", C.c_void_p), ("table_out", C.c_void_p), ("valid_out", C.c_void_p)]
 
 
+# device-side box selection (include/cvgs_hip_ext.h: cvgs_boxes_select)
+CAND_XYXY_F32, CAND_CXCYWH_F32 = 0, 1
+SELECT_MAX_FRAMES, SELECT_MAX_PRE_NMS = 16, 1024
+
+
+class BoxSelectDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("frame_width", C.c_int32), ("frame_height", C.c_int32),
+                ("box_format", C.c_int32), ("max_candidates", C.c_int32), ("boxes", C.c_void_p), ("scores", C.c_void_p),
+                ("classes", C.c_void_p), ("count", C.c_void_p), ("box_stride", C.c_int32), ("score_stride", C.c_int32),
+                ("class_stride", C.c_int32), ("pre_nms_k", C.c_int32), ("max_out", C.c_int32), ("reserved", C.c_int32),
+                ("score_threshold", C.c_float), ("iou_threshold", C.c_float), ("xform", C.c_float * 4), ("scratch", C.c_void_p),
+                ("boxes_out", C.c_void_p), ("count_out", C.c_void_p), ("scores_out", C.c_void_p), ("index_out", C.c_void_p)]
+
+
 # every symbol include/cvgs_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("cvgs_abi_version", C.c_int, []),
@@ -175,6 +189,9 @@ SYMBOLS = [
     ("cvgs_warp_table_bytes", C.c_size_t, [C.c_int32]),
     ("cvgs_warp_tables_from_points", C.c_int, [C.POINTER(WarpTableDesc), C.c_int32, C.c_void_p]),
     ("cvgs_warp_table_build_host", C.c_int, [C.POINTER(WarpTableDesc), C.c_void_p]),
+    ("cvgs_boxes_select_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32]),
+    ("cvgs_boxes_select", C.c_int, [C.POINTER(BoxSelectDesc), C.c_int32, C.c_void_p]),
+    ("cvgs_boxes_select_host", C.c_int, [C.POINTER(BoxSelectDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cvgs_range_push", None, [C.c_char_p]),
     ("cvgs_range_pop", None, []),
 ]

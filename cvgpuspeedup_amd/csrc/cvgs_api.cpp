@@ -2048,6 +2048,128 @@ int cvgs_warp_table_build_host(const cvgs_warp_table_desc* desc, void* table_out
     return CVGS_OK;
 }
 
+// Device-side box selection (include/cvgs_hip_ext.h: THE CONTRACT).  Everything is validated here, on the host, before the first HIP
+// call; steps 2-5, the order and the suppression predicate (cvgs_geometry.h) are one text for the kernels (k_select.hip) and for
+// cvgs_boxes_select_host.
+size_t cvgs_boxes_select_scratch_bytes(int32_t max_candidates, int32_t pre_nms_k) {
+    if (max_candidates < 1 || max_candidates > 65535 || pre_nms_k < 1 || pre_nms_k > CVGS_SELECT_MAX_PRE_NMS) return 0;
+    return select_scratch_bytes(pre_nms_k);
+}
+
+namespace {
+// `host`: cvgs_boxes_select_host -- desc.scratch and the descriptor's output pointers are not used
+int check_select_desc(const cvgs_box_select_desc& d, bool host, SelectFrame& f) {
+    if (d.struct_size != sizeof(cvgs_box_select_desc)) return fail(CVGS_ERR_INVALID, "cvgs_box_select_desc size mismatch (ABI)");
+    if (d.flags) return fail(CVGS_ERR_INVALID, "boxes_select: flags must be 0");
+    if (d.frame_width < 1 || d.frame_height < 1) return fail(CVGS_ERR_INVALID, "boxes_select: frame_width / frame_height must be positive");
+    if (d.frame_width > kMaxDim || d.frame_height > kMaxDim) return fail(CVGS_ERR_UNSUPPORTED, "boxes_select: frame wider or taller than 2^24 pixels");
+    if (d.box_format != CVGS_CAND_XYXY_F32 && d.box_format != CVGS_CAND_CXCYWH_F32) return fail(CVGS_ERR_INVALID, "boxes_select: bad box format");
+    if (d.max_candidates < 1 || d.max_candidates > 65535) return fail(CVGS_ERR_INVALID, "boxes_select: max_candidates must be in [1, 65535]");
+    if (!d.boxes) return fail(CVGS_ERR_INVALID, "boxes_select: boxes is null");
+    if (!d.scores) return fail(CVGS_ERR_INVALID, "boxes_select: scores is null");
+    if (d.box_stride < 4) return fail(CVGS_ERR_INVALID, "boxes_select: box_stride must be at least 4 floats");
+    if (d.score_stride < 1) return fail(CVGS_ERR_INVALID, "boxes_select: score_stride must be at least 1 float");
+    if (d.classes && d.class_stride < 1) return fail(CVGS_ERR_INVALID, "boxes_select: class_stride must be at least 1 with classes");
+    if (d.pre_nms_k < 1 || d.pre_nms_k > CVGS_SELECT_MAX_PRE_NMS) return fail(CVGS_ERR_INVALID, "boxes_select: pre_nms_k must be in [1, 1024]");
+    if (d.max_out < 1 || d.max_out > d.pre_nms_k) return fail(CVGS_ERR_INVALID, "boxes_select: max_out must be in [1, pre_nms_k]");
+    if (d.reserved) return fail(CVGS_ERR_INVALID, "boxes_select: reserved must be 0");
+    if (d.score_threshold != d.score_threshold) return fail(CVGS_ERR_INVALID, "boxes_select: score_threshold is NaN");
+    if (!(d.iou_threshold >= 0.0f && d.iou_threshold <= 1.0f)) return fail(CVGS_ERR_INVALID, "boxes_select: iou_threshold must be in [0, 1]");
+    if (!fit_finite((double)d.xform[0]) || !fit_finite((double)d.xform[1]) || !(d.xform[0] > 0.0f) || !(d.xform[1] > 0.0f))
+        return fail(CVGS_ERR_INVALID, "boxes_select: xform scales (sx, sy) must be finite and positive");
+    if (!fit_finite((double)d.xform[2]) || !fit_finite((double)d.xform[3])) return fail(CVGS_ERR_INVALID, "boxes_select: xform offsets (ox, oy) must be finite");
+    if (((uintptr_t)d.boxes | (uintptr_t)d.scores | (uintptr_t)d.classes | (uintptr_t)d.count) & 3)
+        return fail(CVGS_ERR_INVALID, "boxes_select: boxes / scores / classes / count need 4-byte alignment");
+    if (!host) {
+        if (!d.scratch) return fail(CVGS_ERR_INVALID, "boxes_select: scratch is null");
+        if (!d.boxes_out) return fail(CVGS_ERR_INVALID, "boxes_select: boxes_out is null");
+        if (!d.count_out) return fail(CVGS_ERR_INVALID, "boxes_select: count_out is null");
+        if (((uintptr_t)d.scratch & 7) || (((uintptr_t)d.boxes_out | (uintptr_t)d.count_out | (uintptr_t)d.scores_out | (uintptr_t)d.index_out) & 3))
+            return fail(CVGS_ERR_INVALID, "boxes_select: scratch needs 8-byte, boxes_out / count_out / scores_out / index_out 4-byte alignment");
+    }
+    f = SelectFrame{};
+    f.boxes = d.boxes; f.scores = d.scores; f.classes = d.classes; f.count = d.count;
+    if (!host) {
+        f.scratch = (uint8_t*)d.scratch;
+        f.boxes_out = d.boxes_out; f.count_out = d.count_out; f.scores_out = d.scores_out; f.index_out = d.index_out;
+    }
+    f.w = d.frame_width; f.h = d.frame_height; f.fmt = d.box_format; f.max_cand = d.max_candidates;
+    f.box_stride = d.box_stride; f.score_stride = d.score_stride; f.class_stride = d.classes ? d.class_stride : 0;
+    f.pre_k = d.pre_nms_k; f.max_out = d.max_out;
+    f.score_thr = d.score_threshold; f.iou_thr = d.iou_threshold;
+    for (int k = 0; k < 4; ++k) f.xf[k] = d.xform[k];
+    return CVGS_OK;
+}
+} // namespace
+
+int cvgs_boxes_select(const cvgs_box_select_desc* descs, int32_t n, cvgs_stream_t stream) {
+    if (!descs) return fail(CVGS_ERR_INVALID, "boxes_select: null descriptors");
+    if (n < 1 || n > CVGS_SELECT_MAX_FRAMES) return fail(CVGS_ERR_INVALID, "boxes_select: n must be in [1, 16]");
+    SelectFrame frames[CVGS_SELECT_MAX_FRAMES];
+    ByteRange outs[5 * CVGS_SELECT_MAX_FRAMES];
+    int n_outs = 0;
+    for (int i = 0; i < n; ++i) {
+        const int rc = check_select_desc(descs[i], false, frames[i]);
+        if (rc) return rc;
+        const SelectFrame& f = frames[i];
+        outs[n_outs++] = ByteRange{f.scratch, f.scratch + select_scratch_bytes(f.pre_k)};
+        outs[n_outs++] = ByteRange{(const uint8_t*)f.boxes_out, (const uint8_t*)f.boxes_out + (size_t)f.max_out * 4 * sizeof(float)};
+        outs[n_outs++] = ByteRange{(const uint8_t*)f.count_out, (const uint8_t*)f.count_out + sizeof(int32_t)};
+        if (f.scores_out) outs[n_outs++] = ByteRange{(const uint8_t*)f.scores_out, (const uint8_t*)f.scores_out + (size_t)f.max_out * sizeof(float)};
+        if (f.index_out) outs[n_outs++] = ByteRange{(const uint8_t*)f.index_out, (const uint8_t*)f.index_out + (size_t)f.max_out * sizeof(int32_t)};
+    }
+    for (int i = 0; i < n_outs; ++i)
+        for (int j = 0; j < i; ++j)
+            if (outs[i].lo < outs[j].hi && outs[j].lo < outs[i].hi) return fail(CVGS_ERR_INVALID, "boxes_select: the output and scratch buffers of one call overlap");
+    const int e = launch_select(frames, n, stream);
+    if (e) return hip_fail((hipError_t)e, "boxes_select: kernel launch");
+    return CVGS_OK;
+}
+
+int cvgs_boxes_select_host(const cvgs_box_select_desc* desc, void* boxes_out, int32_t* count_out, float* scores_out, int32_t* index_out) {
+    if (!desc || !boxes_out || !count_out) return fail(CVGS_ERR_INVALID, "boxes_select_host: null argument");
+    SelectFrame f;
+    const int rc = check_select_desc(*desc, true, f);
+    if (rc) return rc;
+    int live = f.count ? *f.count : f.max_cand;
+    live = live < 0 ? 0 : (live > f.max_cand ? f.max_cand : live);
+    struct Cand {
+        float box[4], score;
+        int32_t index, cls;
+    };
+    std::vector<Cand> work; // steps 2-5, then step 6: the order k_select_rank finds by counting
+    for (int i = 0; i < live; ++i) {
+        const float* q = f.boxes + (size_t)i * (size_t)f.box_stride;
+        Cand c;
+        c.score = f.scores[(size_t)i * (size_t)f.score_stride];
+        c.index = i;
+        if (!select_prepare(f.fmt, q[0], q[1], q[2], q[3], c.score, f.score_thr, f.xf, f.w, f.h, c.box)) continue;
+        c.cls = f.classes ? f.classes[(size_t)i * (size_t)f.class_stride] : 0;
+        work.push_back(c);
+    }
+    std::sort(work.begin(), work.end(), [](const Cand& a, const Cand& b) { return select_precedes(a.score, a.index, b.score, b.index); });
+    if (work.size() > (size_t)f.pre_k) work.resize((size_t)f.pre_k);
+    std::vector<int> kept; // step 7
+    for (size_t i = 0; i < work.size() && (int)kept.size() < f.max_out; ++i) {
+        const Cand& c = work[i];
+        bool sup = false;
+        for (size_t k = 0; k < kept.size() && !sup; ++k) {
+            const Cand& j = work[(size_t)kept[k]];
+            sup = j.cls == c.cls && select_suppresses(j.box[0], j.box[1], j.box[2], j.box[3], c.box[0], c.box[1], c.box[2], c.box[3], f.iou_thr);
+        }
+        if (!sup) kept.push_back((int)i);
+    }
+    float* bo = (float*)boxes_out; // step 8: every element
+    for (int k = 0; k < f.max_out; ++k) {
+        const Cand* c = k < (int)kept.size() ? &work[(size_t)kept[(size_t)k]] : nullptr;
+        for (int e = 0; e < 4; ++e) bo[(size_t)k * 4 + e] = c ? c->box[e] : 0.0f;
+        if (scores_out) scores_out[k] = c ? c->score : 0.0f;
+        if (index_out) index_out[k] = c ? c->index : -1;
+    }
+    *count_out = (int32_t)kept.size();
+    return CVGS_OK;
+}
+
 // ---- CircularTensor (the handle and the update routes: in front of this block) ---------------------------------
 int cvgs_circular_create(cvgs_circular_t* out, int32_t width, int32_t height, int32_t elem_type,
                          int32_t color_planes, int32_t batch, int32_t order, int32_t cp_mode, int32_t device_id) {

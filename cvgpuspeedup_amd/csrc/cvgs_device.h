@@ -369,6 +369,32 @@ static_assert(sizeof(PointFrame) * CVGS_WARP_MAX_FRAMES <= 4096, "the descriptor
 // validated by the caller; frames[0..n), n <= CVGS_WARP_MAX_FRAMES.  0 or a HIP error code
 int launch_points(const PointFrame* frames, int n, void* stream);
 
+// ---- device-side box selection (k_select.hip): one frame's part of a cvgs_boxes_select call, 136 bytes ----------------------------------
+struct SelectFrame {
+    const float* boxes;      // candidate i: boxes[i * box_stride + 0..3]
+    const float* scores;     // candidate i: scores[i * score_stride]
+    const int32_t* classes;  // candidate i: classes[i * class_stride], or nullptr
+    const int32_t* count;    // live candidates, or nullptr = max_cand
+    uint8_t* scratch;        // select_scratch_bytes(pre_k): the working list between the two launches
+    float* boxes_out;        // out: float[max_out][4]
+    int32_t* count_out;      // out: one int32
+    float* scores_out;       // out: float[max_out], or nullptr
+    int32_t* index_out;      // out: int32[max_out], or nullptr
+    int32_t w, h, fmt, max_cand;
+    int32_t box_stride, score_stride, class_stride;
+    int32_t pre_k, max_out;
+    float score_thr, iou_thr;
+    float xf[4];
+    int32_t pad;
+};
+static_assert(sizeof(SelectFrame) == 136, "SelectFrame layout");
+static_assert(sizeof(SelectFrame) * CVGS_SELECT_MAX_FRAMES <= 4096, "the descriptors of one call fit a 4 KB argument block");
+// The working list in scratch: int32 {members, 0}, then seven arrays of pre_k 4-byte values: xa, ya, xb, yb, score, index, class.
+static constexpr int kSelectFields = 7;
+inline size_t select_scratch_bytes(int pre_k) { return 8 + (((size_t)pre_k * kSelectFields * 4 + 7) & ~(size_t)7); }
+// validated by the caller; frames[0..n), n <= CVGS_SELECT_MAX_FRAMES.  Enqueues the rank launch, then the suppress launch.  0 or a HIP error code
+int launch_select(const SelectFrame* frames, int n, void* stream);
+
 // ---- device-side arrival flags of the P2P fused-write exchange (k_exchange.hip) ----------------------------------------------
 #define CVGS_MAX_EXCHANGE_PEERS 16
 int launch_exchange_signal(void* const* peer_flags, int n, uint64_t value, uint64_t* counter, void* stream);

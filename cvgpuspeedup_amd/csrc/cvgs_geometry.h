@@ -146,4 +146,48 @@ CVGS_HD inline bool warp_fit(int fit, int k, const float* pts, const float* tmpl
     return true;
 }
 
+// ---- detector candidates -> selected boxes (cvgs_hip_ext.h: cvgs_boxes_select, THE CONTRACT) ---------------------------------------------
+// Steps 2-5 for ONE live candidate: `c` = its four coordinates as read, `xf` = (sx, sy, ox, oy).  Returns whether it is a member; then
+// out[0..3] = (xa, ya, xb, yb) clamped into the frame.  Strict fp32, one rounding per operation in the order written (both sides compile
+// this with -ffp-contract=off); the clamp is spelled with comparisons so that -0.0f and a NaN from inf - inf both give +0.0f on either side.
+CVGS_HD inline float select_clamp(float v, float e) {
+    v = v > 0.0f ? v : 0.0f;
+    return v < e ? v : e;
+}
+CVGS_HD inline bool select_prepare(int fmt, float c0, float c1, float c2, float c3, float score, float score_thr, const float* xf, int w, int h, float* out) {
+    if (score != score || !(score >= score_thr) || c0 != c0 || c1 != c1 || c2 != c2 || c3 != c3) return false;
+    float xa = c0, ya = c1, xb = c2, yb = c3;
+    if (fmt == CVGS_CAND_CXCYWH_F32) {
+        const float hw = c2 * 0.5f, hh = c3 * 0.5f;
+        xa = c0 - hw;
+        xb = c0 + hw;
+        ya = c1 - hh;
+        yb = c1 + hh;
+    }
+    xa = xa * xf[0]; xa = xa + xf[2];
+    xb = xb * xf[0]; xb = xb + xf[2];
+    ya = ya * xf[1]; ya = ya + xf[3];
+    yb = yb * xf[1]; yb = yb + xf[3];
+    const float fw = (float)w, fh = (float)h;
+    xa = select_clamp(xa, fw);
+    xb = select_clamp(xb, fw);
+    ya = select_clamp(ya, fh);
+    yb = select_clamp(yb, fh);
+    out[0] = xa; out[1] = ya; out[2] = xb; out[3] = yb;
+    return xb > xa && yb > ya;
+}
+// Step 6: member j (score sj) comes before member i (score si).  A strict total order over members: no score is NaN.
+CVGS_HD inline bool select_precedes(float sj, int j, float si, int i) { return sj > si || (sj == si && j < i); }
+// Step 7: the kept box (jxa .. jyb) suppresses the box (ixa .. iyb).  Clamped boxes: every value lies in [0, extent], none is NaN or -0.
+CVGS_HD inline bool select_suppresses(float jxa, float jya, float jxb, float jyb, float ixa, float iya, float ixb, float iyb, float iou_thr) {
+    const float iw = fminf(ixb, jxb) - fmaxf(ixa, jxa);
+    const float ih = fminf(iyb, jyb) - fmaxf(iya, jya);
+    if (!(iw > 0.0f && ih > 0.0f)) return false;
+    const float inter = iw * ih;
+    const float area_i = (ixb - ixa) * (iyb - iya);
+    const float area_j = (jxb - jxa) * (jyb - jya);
+    const float uni = (area_i + area_j) - inter;
+    return inter > iou_thr * uni;
+}
+
 } // namespace cvgs

@@ -793,6 +793,81 @@ def resize_boxes(frame, table, max_boxes, dsize, background=None, ar=IGNORE_AR, 
     return rd
 
 
+# ---- device-side box selection: score threshold, top-K, greedy NMS (include/cvgs_hip_ext.h: cvgs_boxes_select) ----------------
+CAND_XYXY_F32, CAND_CXCYWH_F32 = capi.CAND_XYXY_F32, capi.CAND_CXCYWH_F32
+
+
+def boxes_select_scratch_bytes(max_candidates, pre_nms_k):
+    """cvgs_boxes_select_scratch_bytes: the size of the `scratch` buffer of one frame (0 for arguments out of range)."""
+    return int(capi.load_library().cvgs_boxes_select_scratch_bytes(int(max_candidates), int(pre_nms_k)))
+
+
+def box_select_desc(frame_size, boxes, scores, max_candidates, scratch, boxes_out, count_out, score_threshold, iou_threshold, pre_nms_k, max_out,
+                    box_format=CAND_XYXY_F32, box_stride=4, score_stride=1, classes=None, class_stride=1, count=None, xform=(1.0, 1.0, 0.0, 0.0),
+                    scores_out=None, index_out=None):
+    """One cvgs_box_select_desc: frame_size = (width, height) of the frame the boxes are clamped into; boxes / scores / classes / count /
+    scratch and the outputs are device buffers (torch tensors or raw pointers; strides in elements, so a [N, 4 + 1 + C] head is read in
+    place); xform = (sx, sy, ox, oy) maps detector coordinates to frame pixels (letterbox_xform)."""
+    d = capi.BoxSelectDesc()
+    d.struct_size = C.sizeof(capi.BoxSelectDesc)
+    d.frame_width, d.frame_height = int(frame_size[0]), int(frame_size[1])
+    d.box_format, d.max_candidates = box_format, int(max_candidates)
+    d.boxes, d.scores, d.classes, d.count = _dev_ptr(boxes) or None, _dev_ptr(scores) or None, _dev_ptr(classes) or None, _dev_ptr(count) or None
+    d.box_stride, d.score_stride, d.class_stride = int(box_stride), int(score_stride), int(class_stride)
+    d.pre_nms_k, d.max_out = int(pre_nms_k), int(max_out)
+    d.score_threshold, d.iou_threshold = float(score_threshold), float(iou_threshold)
+    for i, v in enumerate(xform):
+        d.xform[i] = float(v)
+    d.scratch, d.boxes_out, d.count_out = _dev_ptr(scratch) or None, _dev_ptr(boxes_out) or None, _dev_ptr(count_out) or None
+    d.scores_out, d.index_out = _dev_ptr(scores_out) or None, _dev_ptr(index_out) or None
+    return d
+
+
+def boxes_select(stream, descs):
+    """cvgs_boxes_select: two small kernels on `stream` (rank, suppress) select the boxes of every desc (box_select_desc, at most 16);
+    nothing is copied to the host, nothing synchronises, and the call can be captured in front of plane_tables_from_boxes."""
+    lib = capi.load_library()
+    descs = list(descs)
+    arr = (capi.BoxSelectDesc * len(descs))(*descs)
+    capi.check(lib.cvgs_boxes_select(arr, len(descs), stream_handle(stream)))
+
+
+def boxes_select_host(desc, boxes, scores, classes=None, count=None):
+    """cvgs_boxes_select_host: (boxes_out float32 [max_out, 4], count, scores_out float32 [max_out], index_out int32 [max_out]) -- the bytes
+    the kernels must write for `desc` -- computed on the CPU from HOST arrays: `boxes` / `scores` / `classes` are float32 / float32 / int32
+    numpy arrays addressed with the descriptor's strides (they may be views of one array), `count` an int or None."""
+    import numpy as np
+    lib = capi.load_library()
+    d = capi.BoxSelectDesc.from_buffer_copy(desc)
+    for name, arr, dt in (("boxes", boxes, np.float32), ("scores", scores, np.float32), ("classes", classes, np.int32)):
+        if arr is not None and (not isinstance(arr, np.ndarray) or arr.dtype != dt):
+            raise ValueError("%s must be a numpy array of %s" % (name, np.dtype(dt).name))
+    cnt = None if count is None else C.c_int32(int(count))
+    d.boxes, d.scores = boxes.ctypes.data, scores.ctypes.data
+    d.classes = None if classes is None else classes.ctypes.data
+    d.count = None if cnt is None else C.addressof(cnt)
+    n = max(int(d.max_out), 1)
+    bo, so, io = np.empty((n, 4), np.float32), np.empty((n,), np.float32), np.empty((n,), np.int32)
+    co = C.c_int32(-1)
+    capi.check(lib.cvgs_boxes_select_host(C.byref(d), bo.ctypes.data, C.addressof(co), so.ctypes.data, io.ctypes.data))
+    return bo, int(co.value), so, io
+
+
+def letterbox_xform(frame_size, det_size, ar=IGNORE_AR):
+    """The xform (sx, sy, ox, oy) of box_select_desc for a detector that saw the whole frame through cvgs.resize(..., det_size, ..., ar):
+    the resize kernels read destination pixel (x, y) at source (x - x1) * fx, (y - y1) * fy, so a detector coordinate maps to the frame as
+    x * fx + (-(x1 * fx)).  fx, fy, x1, y1 are read from the plane table cvgs.build_plane_table writes for that chain (float32)."""
+    import numpy as np
+    w, h = int(frame_size[0]), int(frame_size[1])
+    dummy = np.zeros(16, np.uint8)  # (the table builder never reads the frame)
+    whole = GpuMat(h, w, make_type(DEPTH_8U, 1), dummy.ctypes.data, w, owner=dummy)
+    raw = np.frombuffer(build_plane_table(resize(whole.cv_type, INTER_LINEAR, [whole], (int(det_size[0]), int(det_size[1])), 1, None, ar)), np.uint8)
+    fx, fy = raw[20:28].view(np.float32)
+    x1, y1 = raw[28:36].view(np.int32)
+    zero = np.float32(0.0)  # (0 - x, not -x: an offset of +0.0 without padding)
+    return (float(fx), float(fy), float(zero - np.float32(x1) * fx), float(zero - np.float32(y1) * fy))
+
+
 # ---- device-built warp tables: aligned crops from a detector's device-side landmarks (include/cvgs_hip_ext.h) ----------------
 WARP_FIT_SIMILARITY, WARP_FIT_AFFINE3 = capi.WARP_FIT_SIMILARITY, capi.WARP_FIT_AFFINE3
 

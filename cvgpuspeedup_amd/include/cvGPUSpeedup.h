@@ -690,6 +690,79 @@ private:
     AspectRatio ar_ = IGNORE_AR;
 };
 
+// ---- the detector's raw candidates -> the boxes DeviceCrops reads (engine extension: cvgs_boxes_select, include/cvgs_hip_ext.h) --------
+// Score threshold, top-K and greedy NMS on the device, in frame coordinates: two small kernels on the stream, nothing copied to the host.
+//   cvGS::DeviceBoxSelect select(cv::Size(1920, 1080), 8400, 1024, 50);     // owns scratch and outputs for 8400 candidates, 50 boxes
+//   select.candidates(d_head, 6, d_head + 4, 6);                            // a [8400, 6] head read in place: boxes, then scores
+//   select.thresholds(0.25f, 0.45f).transform(sx, sy, ox, oy);              // detector input -> frame pixels
+//   select.enqueue(stream);
+//   crops.update(stream, frame, select.boxes(), select.count(), CVGS_BOX_XYXY_F32, cv::Size(64, 128));   // crops: DeviceCrops(50)
+// The second constructor takes caller-owned buffers (scratch: cvgs_boxes_select_scratch_bytes) and allocates nothing.
+class DeviceBoxSelect {
+public:
+    DeviceBoxSelect(const cv::Size& frameSize, int maxCandidates, int preNmsK, int maxOut, bool withScoresAndIndices = true) {
+        init(frameSize, maxCandidates, preNmsK, maxOut);
+        const size_t sb = cvgs_boxes_select_scratch_bytes(maxCandidates, preNmsK);
+        if (!sb || maxOut < 1 || maxOut > preNmsK) throw std::runtime_error("cvGS::DeviceBoxSelect: maxCandidates in [1, 65535], preNmsK in [1, 1024], maxOut in [1, preNmsK]");
+        d_.scratch = own(sb);
+        d_.boxes_out = static_cast<float*>(own((size_t)maxOut * 4 * sizeof(float)));
+        d_.count_out = static_cast<int32_t*>(own(sizeof(int32_t)));
+        if (withScoresAndIndices) {
+            d_.scores_out = static_cast<float*>(own((size_t)maxOut * sizeof(float)));
+            d_.index_out = static_cast<int32_t*>(own((size_t)maxOut * sizeof(int32_t)));
+        }
+    }
+    DeviceBoxSelect(const cv::Size& frameSize, int maxCandidates, int preNmsK, int maxOut, void* scratch, float* boxesOut, int32_t* countOut,
+                    float* scoresOut = nullptr, int32_t* indexOut = nullptr) {
+        init(frameSize, maxCandidates, preNmsK, maxOut);
+        d_.scratch = scratch; d_.boxes_out = boxesOut; d_.count_out = countOut; d_.scores_out = scoresOut; d_.index_out = indexOut;
+    }
+    // where the candidates are (device pointers, strides in elements); classes == nullptr: class-agnostic suppression; count == nullptr: all
+    DeviceBoxSelect& candidates(const float* boxes, int boxStride, const float* scores, int scoreStride, cvgs_cand_format format = CVGS_CAND_XYXY_F32,
+                                const int32_t* classes = nullptr, int classStride = 1, const int32_t* count = nullptr) {
+        d_.boxes = boxes; d_.box_stride = boxStride; d_.scores = scores; d_.score_stride = scoreStride; d_.box_format = (int32_t)format;
+        d_.classes = classes; d_.class_stride = classStride; d_.count = count;
+        return *this;
+    }
+    DeviceBoxSelect& thresholds(float score, float iou) { d_.score_threshold = score; d_.iou_threshold = iou; return *this; }
+    DeviceBoxSelect& transform(float sx, float sy, float ox, float oy) { d_.xform[0] = sx; d_.xform[1] = sy; d_.xform[2] = ox; d_.xform[3] = oy; return *this; }
+    void enqueue(const cv::cuda::Stream& stream) const { fk::detail::check_status(cvgs_boxes_select(&d_, 1, cv::cuda::StreamAccessor::getStream(stream))); }
+    // several frames (the cameras of a tick, at most 16) in ONE call
+    static void enqueue(const cv::cuda::Stream& stream, const std::vector<const DeviceBoxSelect*>& jobs) {
+        std::vector<cvgs_box_select_desc> d;
+        d.reserve(jobs.size());
+        for (const DeviceBoxSelect* j : jobs) {
+            if (!j) throw std::runtime_error("cvGS::DeviceBoxSelect::enqueue: null DeviceBoxSelect");
+            d.push_back(j->d_);
+        }
+        fk::detail::check_status(cvgs_boxes_select(d.data(), (int32_t)d.size(), cv::cuda::StreamAccessor::getStream(stream)));
+    }
+    // what DeviceCrops::update accepts: maxOut x 4 floats (CVGS_BOX_XYXY_F32) and the count
+    const void* boxes() const { return d_.boxes_out; }
+    const int32_t* count() const { return d_.count_out; }
+    const float* scores() const { return d_.scores_out; }   // nullptr when built without
+    const int32_t* indices() const { return d_.index_out; } // nullptr when built without
+    int maxOut() const { return d_.max_out; }
+    const cvgs_box_select_desc& desc() const { return d_; }
+private:
+    void init(const cv::Size& frameSize, int maxCandidates, int preNmsK, int maxOut) {
+        std::memset(&d_, 0, sizeof(d_));
+        d_.struct_size = sizeof(d_);
+        d_.frame_width = frameSize.width; d_.frame_height = frameSize.height;
+        d_.max_candidates = maxCandidates; d_.pre_nms_k = preNmsK; d_.max_out = maxOut;
+        d_.box_format = CVGS_CAND_XYXY_F32; d_.box_stride = 4; d_.score_stride = 1;
+        d_.xform[0] = 1.f; d_.xform[1] = 1.f;
+    }
+    void* own(size_t bytes) {
+        void* p = nullptr;
+        fk::hip_check(hipMalloc(&p, bytes), "hipMalloc(box selection)");
+        owned_.push_back(std::shared_ptr<void>(p, [](void* q) { (void)hipFree(q); }));
+        return p;
+    }
+    cvgs_box_select_desc d_;
+    std::vector<std::shared_ptr<void>> owned_;
+};
+
 // resize<T, INTER_LINEAR | INTER_AREA, AR>(deviceCrops, backgroundValue): the batched read over the device-built table -- maxBoxes planes of the size and
 // aspect-ratio mode of the last update() (AR must be that mode), invalid boxes and the AR padding take backgroundValue.  fk::executeDivergentBatch
 // keeps refusing device tables (it selects planes on the host).

@@ -265,6 +265,82 @@ size_t cvgs_warp_table_bytes(int32_t planes);
 int cvgs_warp_tables_from_points(const cvgs_warp_table_desc* descs, int32_t n, cvgs_stream_t stream);
 int cvgs_warp_table_build_host(const cvgs_warp_table_desc* desc, void* table_out_host);
 
+/* ---- device-side box selection: score threshold, top-K, greedy NMS ---------------------------------------------------------------------
+ * What sits between a detector and cvgs_plane_tables_from_boxes.  A detector emits thousands of scored candidates, usually in the
+ * coordinates of its letterboxed input; the final detections are the few that pass a score threshold and survive non-maximum
+ * suppression, in frame coordinates.  cvgs_boxes_select enqueues TWO small kernels on `stream` (csrc/k_select.hip: rank, then suppress)
+ * for up to 16 frames and nothing else: no allocation, no staging, no copy, no synchronisation, so the call can be captured between the
+ * detector and the table builder.  boxes_out / count_out are by construction a valid boxes / count pair of a CVGS_BOX_XYXY_F32
+ * cvgs_box_table_desc with max_boxes = max_out.  Its cost: see README.md.
+ *
+ * THE CONTRACT.  Arithmetic is strict fp32 (-ffp-contract=off), every operation rounded once, in the order written here; the text is
+ * ONE spelling for the kernels and for cvgs_boxes_select_host (csrc/cvgs_geometry.h: select_prepare, select_precedes,
+ * select_suppresses), so the device writes the host entry's bytes.  There is no division and no sort whose tie order could differ.
+ * Candidate i of a frame reads boxes[i * box_stride + 0..3], scores[i * score_stride] and (if given) classes[i * class_stride]: a
+ * [N, 4 + 1 + C] detector head is read in place, and the three pointers may point into one tensor.  Per frame:
+ *   1. live = clamp(count ? *count : max_candidates, 0, max_candidates).
+ *   2. Candidate i < live is a MEMBER iff its score is not NaN, score >= score_threshold, and none of its four coordinates is NaN.
+ *   3. To XYXY.  CVGS_CAND_XYXY_F32: (xa, ya, xb, yb) as read.  CVGS_CAND_CXCYWH_F32 (cx, cy, w, h): hw = w * 0.5f; xa = cx - hw;
+ *      xb = cx + hw; hh = h * 0.5f; ya = cy - hh; yb = cy + hh.
+ *   4. To frame coordinates with xform = (sx, sy, ox, oy): xa = xa * sx; xa = xa + ox (two roundings, no fma); the same for xb, and
+ *      for ya and yb with sy, oy.
+ *   5. Clamp: xa = fminf(fmaxf(xa, 0.0f), (float)W), the same for xb, and with H for ya and yb -- spelled v > 0.0f ? v : 0.0f, then
+ *      v < e ? v : e, which pins the two cases fmaxf leaves open: -0.0f, and a NaN formed by inf - inf in step 3, both give +0.0f.
+ *      A candidate stays a member iff xb > xa && yb > ya.
+ *   6. Members are ordered by score descending, equal scores (-0.0f == 0.0f) by lower index first.  The first min(members, pre_nms_k)
+ *      form the WORKING LIST.
+ *   7. Greedy walk of the working list in that order.  A candidate is KEPT iff no earlier kept candidate suppresses it; with `classes`,
+ *      only earlier kept candidates of the same class value count.  j suppresses i iff
+ *        iw = fminf(xb_i, xb_j) - fmaxf(xa_i, xa_j), iw > 0.0f;   ih = fminf(yb_i, yb_j) - fmaxf(ya_i, ya_j), ih > 0.0f;
+ *        inter = iw * ih;   area = (xb - xa) * (yb - ya) for i and for j;   uni = (area_i + area_j) - inter;
+ *        inter > iou_threshold * uni.
+ *      The walk stops once max_out candidates are kept.
+ *   8. EVERY output element is written on every call: boxes_out[k] = the four clamped floats of the k-th kept candidate for k < kept,
+ *      (0, 0, 0, 0) beyond (cvgs_plane_tables_from_boxes treats that box as invalid); count_out = kept; scores_out[k] = its score as
+ *      read, 0.0f beyond; index_out[k] = its candidate index, -1 beyond.
+ * HOW (csrc/k_select.hip): the rank launch (grid: 256 candidates per workgroup x frame) prepares each candidate and finds its position
+ * in the order of step 6 by COUNTING the members that precede it -- ranks are a permutation, so nothing is sorted and no atomic's order
+ * matters -- and stores the members of rank < pre_nms_k into `scratch`; the suppress launch (one wave per frame) holds the working list
+ * in LDS, walks it and writes every output.  `scratch` (device, 8-byte aligned, cvgs_boxes_select_scratch_bytes(max_candidates,
+ * pre_nms_k) bytes -- 0 for arguments out of range) belongs to the call from its enqueue to the end of the suppress launch; its
+ * contents before and after are unspecified.
+ * Validation happens completely on the host before the first HIP call (a machine without a GPU can test it): null descriptors, null
+ * boxes / scores / scratch / boxes_out / count_out, struct_size, flags, n outside 1..16, frame_width / frame_height < 1, a bad
+ * box_format, max_candidates outside 1..65535, box_stride < 4, score_stride < 1, class_stride < 1 with classes, pre_nms_k outside
+ * 1..1024, max_out outside 1..pre_nms_k, misaligned pointers (4 bytes; scratch: 8), iou_threshold outside [0, 1] or NaN, a NaN
+ * score_threshold, sx or sy not finite or <= 0, ox or oy not finite, output or scratch buffers of one call that overlap ->
+ * CVGS_ERR_INVALID; a frame beyond CVGS_MAX_DIM -> CVGS_ERR_UNSUPPORTED.
+ *   cvgs_boxes_select_host  the same descriptor with HOST boxes / scores / classes / count; desc's scratch and output pointers are
+ *                           ignored and the results go to boxes_out (float[max_out][4]), count_out, scores_out and index_out (the last
+ *                           two optional).  Runs the shared text on the CPU and writes the bytes the kernels must write; makes no
+ *                           HIP call.
+ * No reference counterpart.                                                                                                          */
+typedef enum cvgs_cand_format { CVGS_CAND_XYXY_F32 = 0, CVGS_CAND_CXCYWH_F32 = 1 } cvgs_cand_format;
+#define CVGS_SELECT_MAX_FRAMES 16
+#define CVGS_SELECT_MAX_PRE_NMS 1024
+typedef struct cvgs_box_select_desc {
+    uint32_t struct_size, flags;          /* sizeof(cvgs_box_select_desc); flags: must be 0 */
+    int32_t frame_width, frame_height;    /* 1..CVGS_MAX_DIM: what the boxes are clamped into */
+    int32_t box_format, max_candidates;   /* cvgs_cand_format; 1..65535 */
+    const float* boxes;                   /* device: candidate i at boxes[i * box_stride + 0..3] */
+    const float* scores;                  /* device: candidate i at scores[i * score_stride] */
+    const int32_t* classes;               /* device: candidate i at classes[i * class_stride], or NULL (class-agnostic) */
+    const int32_t* count;                 /* device, or NULL = max_candidates */
+    int32_t box_stride, score_stride;     /* in floats: >= 4, >= 1 */
+    int32_t class_stride, pre_nms_k;      /* in int32: >= 1 with classes; 1..CVGS_SELECT_MAX_PRE_NMS */
+    int32_t max_out, reserved;            /* 1..pre_nms_k; 0 */
+    float score_threshold, iou_threshold; /* not NaN; [0, 1] */
+    float xform[4];                       /* (sx, sy, ox, oy): frame = detector * s + o */
+    void* scratch;                        /* device, 8-byte aligned, cvgs_boxes_select_scratch_bytes(max_candidates, pre_nms_k) */
+    float* boxes_out;                     /* device float[max_out][4] */
+    int32_t* count_out;                   /* device int32 */
+    float* scores_out;                    /* device float[max_out], or NULL */
+    int32_t* index_out;                   /* device int32[max_out], or NULL */
+} cvgs_box_select_desc;
+size_t cvgs_boxes_select_scratch_bytes(int32_t max_candidates, int32_t pre_nms_k);
+int cvgs_boxes_select(const cvgs_box_select_desc* descs, int32_t n, cvgs_stream_t stream); /* n = 1..CVGS_SELECT_MAX_FRAMES frames, one call */
+int cvgs_boxes_select_host(const cvgs_box_select_desc* desc, void* boxes_out, int32_t* count_out, float* scores_out, int32_t* index_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,19 @@ class BoxSelectDesc(C.Structure):
                 ("boxes_out", C.c_void_p), ("count_out", C.c_void_p), ("scores_out", C.c_void_p), ("index_out", C.c_void_p)]
 
 
+# a detector's raw head -> select's candidates (include/cvgs_hip_ext.h: cvgs_head_decode)
+HEAD_F32, HEAD_F16, HEAD_BF16 = 0, 1, 2
+HEAD_MAX_FRAMES, HEAD_MAX_CLASSES, HEAD_MAX_ATTR = 16, 4096, 8191
+
+
+class HeadDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("head", C.c_void_p), ("elem_type", C.c_int32),
+                ("max_candidates", C.c_int32), ("cand_stride", C.c_int32), ("attr_stride", C.c_int32), ("box_attr", C.c_int32),
+                ("obj_attr", C.c_int32), ("class_attr", C.c_int32), ("num_classes", C.c_int32), ("score_threshold", C.c_float),
+                ("reserved", C.c_int32), ("scratch", C.c_void_p), ("boxes_out", C.c_void_p), ("scores_out", C.c_void_p),
+                ("classes_out", C.c_void_p), ("index_out", C.c_void_p), ("count_out", C.c_void_p)]
+
+
 # every symbol include/cvgs_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("cvgs_abi_version", C.c_int, []),
@@ -192,6 +205,9 @@ SYMBOLS = [
     ("cvgs_boxes_select_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32]),
     ("cvgs_boxes_select", C.c_int, [C.POINTER(BoxSelectDesc), C.c_int32, C.c_void_p]),
     ("cvgs_boxes_select_host", C.c_int, [C.POINTER(BoxSelectDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("cvgs_head_decode_scratch_bytes", C.c_size_t, [C.c_int32]),
+    ("cvgs_head_decode", C.c_int, [C.POINTER(HeadDesc), C.c_int32, C.c_void_p]),
+    ("cvgs_head_decode_host", C.c_int, [C.POINTER(HeadDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cvgs_range_push", None, [C.c_char_p]),
     ("cvgs_range_pop", None, []),
 ]

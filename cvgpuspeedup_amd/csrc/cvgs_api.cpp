@@ -2170,6 +2170,136 @@ int cvgs_boxes_select_host(const cvgs_box_select_desc* desc, void* boxes_out, in
     return CVGS_OK;
 }
 
+// A detector's raw head -> select's candidates (include/cvgs_hip_ext.h: THE CONTRACT).  Everything is validated here, on the host, before
+// the first HIP call; the widening, the best class in both its forms, the score and the membership test (cvgs_geometry.h) are one text
+// for the kernels (k_head.hip) and for cvgs_head_decode_host.
+size_t cvgs_head_decode_scratch_bytes(int32_t max_candidates) {
+    if (max_candidates < 1 || max_candidates > 65535) return 0;
+    return head_scratch_bytes(max_candidates);
+}
+
+namespace {
+inline size_t head_elem_bytes(int elem) { return elem == CVGS_HEAD_F32 ? 4 : 2; }
+// `host`: cvgs_head_decode_host -- desc.scratch and the descriptor's output pointers are not used
+int check_head_desc(const cvgs_head_desc& d, bool host, HeadFrame& f) {
+    if (d.struct_size != sizeof(cvgs_head_desc)) return fail(CVGS_ERR_INVALID, "cvgs_head_desc size mismatch (ABI)");
+    if (d.flags) return fail(CVGS_ERR_INVALID, "head_decode: flags must be 0");
+    if (d.reserved) return fail(CVGS_ERR_INVALID, "head_decode: reserved must be 0");
+    if (d.elem_type != CVGS_HEAD_F32 && d.elem_type != CVGS_HEAD_F16 && d.elem_type != CVGS_HEAD_BF16) return fail(CVGS_ERR_INVALID, "head_decode: bad elem_type");
+    if (d.max_candidates < 1 || d.max_candidates > 65535) return fail(CVGS_ERR_INVALID, "head_decode: max_candidates must be in [1, 65535]");
+    if (!d.head) return fail(CVGS_ERR_INVALID, "head_decode: head is null");
+    if (d.cand_stride < 1) return fail(CVGS_ERR_INVALID, "head_decode: cand_stride must be at least 1 element");
+    if (d.attr_stride < 1) return fail(CVGS_ERR_INVALID, "head_decode: attr_stride must be at least 1 element");
+    if (d.num_classes < 1 || d.num_classes > CVGS_HEAD_MAX_CLASSES) return fail(CVGS_ERR_INVALID, "head_decode: num_classes must be in [1, 4096]");
+    if (d.box_attr < 0 || d.box_attr + 3 > CVGS_HEAD_MAX_ATTR) return fail(CVGS_ERR_INVALID, "head_decode: box_attr .. box_attr + 3 must lie in [0, 8191]");
+    if (d.obj_attr < -1 || d.obj_attr > CVGS_HEAD_MAX_ATTR) return fail(CVGS_ERR_INVALID, "head_decode: obj_attr must be -1 or lie in [0, 8191]");
+    if (d.class_attr < 0 || d.class_attr > CVGS_HEAD_MAX_ATTR || d.class_attr + d.num_classes - 1 > CVGS_HEAD_MAX_ATTR)
+        return fail(CVGS_ERR_INVALID, "head_decode: class_attr .. class_attr + num_classes - 1 must lie in [0, 8191]");
+    if (d.score_threshold != d.score_threshold) return fail(CVGS_ERR_INVALID, "head_decode: score_threshold is NaN");
+    if ((uintptr_t)d.head & (head_elem_bytes(d.elem_type) - 1)) return fail(CVGS_ERR_INVALID, "head_decode: head needs the alignment of its element type");
+    if (!host) {
+        if (!d.scratch) return fail(CVGS_ERR_INVALID, "head_decode: scratch is null");
+        if (!d.boxes_out) return fail(CVGS_ERR_INVALID, "head_decode: boxes_out is null");
+        if (!d.scores_out) return fail(CVGS_ERR_INVALID, "head_decode: scores_out is null");
+        if (!d.classes_out) return fail(CVGS_ERR_INVALID, "head_decode: classes_out is null");
+        if (!d.count_out) return fail(CVGS_ERR_INVALID, "head_decode: count_out is null");
+        if (((uintptr_t)d.scratch & 7) ||
+            (((uintptr_t)d.boxes_out | (uintptr_t)d.scores_out | (uintptr_t)d.classes_out | (uintptr_t)d.index_out | (uintptr_t)d.count_out) & 3))
+            return fail(CVGS_ERR_INVALID, "head_decode: scratch needs 8-byte, boxes_out / scores_out / classes_out / index_out / count_out 4-byte alignment");
+    }
+    f = HeadFrame{};
+    f.head = d.head;
+    if (!host) {
+        f.scratch = (uint8_t*)d.scratch;
+        f.boxes_out = d.boxes_out; f.scores_out = d.scores_out; f.classes_out = d.classes_out; f.index_out = d.index_out; f.count_out = d.count_out;
+    }
+    f.elem = d.elem_type; f.n = d.max_candidates;
+    f.cand_stride = d.cand_stride; f.attr_stride = d.attr_stride;
+    f.box_attr = d.box_attr; f.obj_attr = d.obj_attr; f.class_attr = d.class_attr; f.num_classes = d.num_classes;
+    f.score_thr = d.score_threshold;
+    // the score launch's form: contiguous attributes are read by a group of lanes per candidate (the next power of two at or above
+    // num_classes, 4 .. 64), everything else by one lane per candidate
+    f.group = 0;
+    if (d.attr_stride == 1) {
+        int g = 4;
+        while (g < 64 && g < d.num_classes) g *= 2;
+        f.group = g;
+    }
+    return CVGS_OK;
+}
+} // namespace
+
+int cvgs_head_decode(const cvgs_head_desc* descs, int32_t n, cvgs_stream_t stream) {
+    if (!descs) return fail(CVGS_ERR_INVALID, "head_decode: null descriptors");
+    if (n < 1 || n > CVGS_HEAD_MAX_FRAMES) return fail(CVGS_ERR_INVALID, "head_decode: n must be in [1, 16]");
+    HeadFrame frames[CVGS_HEAD_MAX_FRAMES];
+    ByteRange outs[6 * CVGS_HEAD_MAX_FRAMES];
+    int n_outs = 0;
+    for (int i = 0; i < n; ++i) {
+        const int rc = check_head_desc(descs[i], false, frames[i]);
+        if (rc) return rc;
+        const HeadFrame& f = frames[i];
+        const size_t N = (size_t)f.n;
+        outs[n_outs++] = ByteRange{f.scratch, f.scratch + head_scratch_bytes(f.n)};
+        outs[n_outs++] = ByteRange{(const uint8_t*)f.boxes_out, (const uint8_t*)f.boxes_out + N * 4 * sizeof(float)};
+        outs[n_outs++] = ByteRange{(const uint8_t*)f.scores_out, (const uint8_t*)f.scores_out + N * sizeof(float)};
+        outs[n_outs++] = ByteRange{(const uint8_t*)f.classes_out, (const uint8_t*)f.classes_out + N * sizeof(int32_t)};
+        outs[n_outs++] = ByteRange{(const uint8_t*)f.count_out, (const uint8_t*)f.count_out + sizeof(int32_t)};
+        if (f.index_out) outs[n_outs++] = ByteRange{(const uint8_t*)f.index_out, (const uint8_t*)f.index_out + N * sizeof(int32_t)};
+    }
+    for (int i = 0; i < n_outs; ++i)
+        for (int j = 0; j < i; ++j)
+            if (outs[i].lo < outs[j].hi && outs[j].lo < outs[i].hi) return fail(CVGS_ERR_INVALID, "head_decode: the output and scratch buffers of one call overlap");
+    const int e = launch_head(frames, n, stream);
+    if (e) return hip_fail((hipError_t)e, "head_decode: kernel launch");
+    return CVGS_OK;
+}
+
+namespace {
+inline float head_host_at(int elem, const void* head, size_t idx) { // step 1
+    if (elem == CVGS_HEAD_F32) return ((const float*)head)[idx];
+    const uint16_t h = ((const uint16_t*)head)[idx];
+    return elem == CVGS_HEAD_F16 ? head_widen_f16(h) : head_widen_bf16(h);
+}
+void head_decode_host(const HeadFrame& f, float* boxes_out, float* scores_out, int32_t* classes_out, int32_t* index_out, int32_t* count_out) {
+    const size_t as = (size_t)f.attr_stride;
+    const bool has_obj = f.obj_attr >= 0;
+    int k = 0;
+    for (int i = 0; i < f.n; ++i) { // steps 1-5, in candidate order
+        const size_t at = (size_t)i * (size_t)f.cand_stride;
+        float best = -INFINITY;
+        int cls = 0;
+        for (int c = 0; c < f.num_classes; ++c) head_best_step(head_host_at(f.elem, f.head, at + (size_t)(f.class_attr + c) * as), c, &best, &cls);
+        const float obj = has_obj ? head_host_at(f.elem, f.head, at + (size_t)f.obj_attr * as) : 0.0f;
+        const float s = head_score(best, has_obj, obj);
+        float co[4];
+        for (int e = 0; e < 4; ++e) co[e] = head_host_at(f.elem, f.head, at + (size_t)(f.box_attr + e) * as);
+        if (!head_member(s, f.score_thr, co[0], co[1], co[2], co[3])) continue;
+        for (int e = 0; e < 4; ++e) boxes_out[(size_t)k * 4 + e] = co[e];
+        scores_out[k] = s;
+        classes_out[k] = cls;
+        if (index_out) index_out[k] = i;
+        ++k;
+    }
+    *count_out = k;
+    for (; k < f.n; ++k) { // step 6
+        for (int e = 0; e < 4; ++e) boxes_out[(size_t)k * 4 + e] = 0.0f;
+        scores_out[k] = 0.0f;
+        classes_out[k] = 0;
+        if (index_out) index_out[k] = -1;
+    }
+}
+} // namespace
+
+int cvgs_head_decode_host(const cvgs_head_desc* desc, float* boxes_out, float* scores_out, int32_t* classes_out, int32_t* index_out, int32_t* count_out) {
+    if (!desc || !boxes_out || !scores_out || !classes_out || !count_out) return fail(CVGS_ERR_INVALID, "head_decode_host: null argument");
+    HeadFrame f;
+    const int rc = check_head_desc(*desc, true, f);
+    if (rc) return rc;
+    head_decode_host(f, boxes_out, scores_out, classes_out, index_out, count_out);
+    return CVGS_OK;
+}
+
 // ---- CircularTensor (the handle and the update routes: in front of this block) ---------------------------------
 int cvgs_circular_create(cvgs_circular_t* out, int32_t width, int32_t height, int32_t elem_type,
                          int32_t color_planes, int32_t batch, int32_t order, int32_t cp_mode, int32_t device_id) {

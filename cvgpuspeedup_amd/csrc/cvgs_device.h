@@ -395,6 +395,31 @@ inline size_t select_scratch_bytes(int pre_k) { return 8 + (((size_t)pre_k * kSe
 // validated by the caller; frames[0..n), n <= CVGS_SELECT_MAX_FRAMES.  Enqueues the rank launch, then the suppress launch.  0 or a HIP error code
 int launch_select(const SelectFrame* frames, int n, void* stream);
 
+// ---- a detector's raw head -> select's candidates (k_head.hip): one frame's part of a cvgs_head_decode call, 96 bytes -----------------------
+struct HeadFrame {
+    const void* head;        // attribute a of candidate i: element i * cand_stride + a * attr_stride
+    uint8_t* scratch;        // head_scratch_bytes(n): tile counts, dense scores, dense class | member codes
+    float* boxes_out;        // out: float[n][4]
+    float* scores_out;       // out: float[n]
+    int32_t* classes_out;    // out: int32[n]
+    int32_t* index_out;      // out: int32[n], or nullptr
+    int32_t* count_out;      // out: one int32
+    int32_t elem, n;         // cvgs_head_elem; candidates
+    int32_t cand_stride, attr_stride;
+    int32_t box_attr, obj_attr, class_attr, num_classes;
+    float score_thr;
+    int32_t group;           // row form (attr_stride == 1): lanes per candidate, a power of two in 4..64; column form: 0
+};
+static_assert(sizeof(HeadFrame) == 96, "HeadFrame layout");
+static_assert(sizeof(HeadFrame) * CVGS_HEAD_MAX_FRAMES <= 4096, "the descriptors of one call fit a 4 KB argument block");
+// Scratch: int32 member counts of the (at most 256) tiles of 256 candidates, then float score[n], then int32 code[n] = class | member << 16.
+static constexpr int kHeadTile = 256;
+static constexpr int kHeadMaxTiles = 256;
+static constexpr int kHeadMemberBit = 1 << 16;
+inline size_t head_scratch_bytes(int n) { return (size_t)kHeadMaxTiles * 4 + (size_t)n * 8; }
+// validated by the caller; frames[0..n), n <= CVGS_HEAD_MAX_FRAMES.  Enqueues the score launch, then the compact launch.  0 or a HIP error code
+int launch_head(const HeadFrame* frames, int n, void* stream);
+
 // ---- device-side arrival flags of the P2P fused-write exchange (k_exchange.hip) ----------------------------------------------
 #define CVGS_MAX_EXCHANGE_PEERS 16
 int launch_exchange_signal(void* const* peer_flags, int n, uint64_t value, uint64_t* counter, void* stream);

@@ -190,4 +190,40 @@ CVGS_HD inline bool select_suppresses(float jxa, float jya, float jxb, float jyb
     return inter > iou_thr * uni;
 }
 
+// ---- a detector's raw head -> select's candidates (cvgs_hip_ext.h: cvgs_head_decode, THE CONTRACT) ------------------------------------------
+// Step 1: every element widens to fp32 exactly.  bf16 is the top half of an fp32; fp16 is re-biased, its subnormals (m * 2^-24) normalised
+// by the position of their leading bit.  Integer operations only, so host and device cannot differ; a NaN keeps its payload (none is stored).
+CVGS_HD inline float head_bits_f32(uint32_t u) {
+    float f;
+    __builtin_memcpy(&f, &u, 4);
+    return f;
+}
+CVGS_HD inline float head_widen_bf16(uint16_t h) { return head_bits_f32((uint32_t)h << 16); }
+CVGS_HD inline float head_widen_f16(uint16_t h) {
+    const uint32_t s = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3ffu;
+    if (e == 31u) return head_bits_f32(s | 0x7f800000u | (m << 13));
+    if (e != 0u) return head_bits_f32(s | ((e + 112u) << 23) | (m << 13));
+    if (m == 0u) return head_bits_f32(s);
+    const uint32_t sh = (uint32_t)__builtin_clz(m) - 21u; // 1..10: the shift that brings the leading bit of m to bit 10
+    return head_bits_f32(s | ((113u - sh) << 23) | (((m << sh) & 0x3ffu) << 13));
+}
+// Step 2, sequential form: class score v of class c, visited in ascending c from (best, cls) = (-inf, 0).  A NaN never wins (v > best is
+// false), the first of equal scores stays (-0.0f == 0.0f), and best carries the winner's bits.
+CVGS_HD inline void head_best_step(float v, int c, float* best, int* cls) {
+    if (v > *best) {
+        *best = v;
+        *cls = c;
+    }
+}
+// Step 2, combining form: (v, c) beats (b, cb).  Over partial results of the sequential form on disjoint class subsets (each visited in
+// ascending c; an empty subset is the identity (-inf, 0)) the maximum under this relation is the sequential result over all classes: no
+// partial result holds a NaN, and a partial (-inf, x) always has x == 0.
+CVGS_HD inline bool head_best_wins(float v, int c, float b, int cb) { return v > b || (v == b && c < cb); }
+// Step 3: one fp32 multiplication with an objectness value, none without.
+CVGS_HD inline float head_score(float best, bool has_obj, float obj) { return has_obj ? obj * best : best; }
+// Step 4.  A NaN score fails score >= thr.
+CVGS_HD inline bool head_member(float score, float thr, float c0, float c1, float c2, float c3) {
+    return score >= thr && !(c0 != c0 || c1 != c1 || c2 != c2 || c3 != c3);
+}
+
 } // namespace cvgs

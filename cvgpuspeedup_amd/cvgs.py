@@ -868,6 +868,61 @@ def letterbox_xform(frame_size, det_size, ar=IGNORE_AR):
     return (float(fx), float(fy), float(zero - np.float32(x1) * fx), float(zero - np.float32(y1) * fy))
 
 
+# ---- a detector's raw head -> select's candidates (include/cvgs_hip_ext.h: cvgs_head_decode) ------------------------------------
+HEAD_F32, HEAD_F16, HEAD_BF16 = capi.HEAD_F32, capi.HEAD_F16, capi.HEAD_BF16
+
+
+def head_decode_scratch_bytes(max_candidates):
+    """cvgs_head_decode_scratch_bytes: the size of the `scratch` buffer of one frame (0 for an argument out of range)."""
+    return int(capi.load_library().cvgs_head_decode_scratch_bytes(int(max_candidates)))
+
+
+def head_desc(head, elem_type, max_candidates, cand_stride, attr_stride, num_classes, score_threshold, scratch, boxes_out, scores_out, classes_out,
+              count_out, index_out=None, box_attr=0, class_attr=4, obj_attr=-1):
+    """One cvgs_head_desc: attribute a of candidate i is element head[i * cand_stride + a * attr_stride] -- a [N, A] head is (A, 1), an
+    [A, N] head (1, N); the four coordinates start at box_attr, the num_classes class scores at class_attr, obj_attr is the objectness
+    attribute or -1.  head / scratch and the outputs are device buffers (torch tensors or raw pointers); the outputs hold max_candidates
+    entries and are what box_select_desc takes as boxes (stride 4), scores, classes and count."""
+    d = capi.HeadDesc()
+    d.struct_size = C.sizeof(capi.HeadDesc)
+    d.head = _dev_ptr(head) or None
+    d.elem_type, d.max_candidates = int(elem_type), int(max_candidates)
+    d.cand_stride, d.attr_stride = int(cand_stride), int(attr_stride)
+    d.box_attr, d.obj_attr, d.class_attr, d.num_classes = int(box_attr), int(obj_attr), int(class_attr), int(num_classes)
+    d.score_threshold = float(score_threshold)
+    d.scratch, d.boxes_out, d.scores_out = _dev_ptr(scratch) or None, _dev_ptr(boxes_out) or None, _dev_ptr(scores_out) or None
+    d.classes_out, d.index_out, d.count_out = _dev_ptr(classes_out) or None, _dev_ptr(index_out) or None, _dev_ptr(count_out) or None
+    return d
+
+
+def head_decode(stream, descs):
+    """cvgs_head_decode: two small kernels on `stream` (score, compact) decode the head of every desc (head_desc, at most 16); nothing
+    is copied to the host, nothing synchronises, and the call can be captured in front of boxes_select."""
+    lib = capi.load_library()
+    descs = list(descs)
+    arr = (capi.HeadDesc * len(descs))(*descs)
+    capi.check(lib.cvgs_head_decode(arr, len(descs), stream_handle(stream)))
+
+
+def head_decode_host(desc, head):
+    """cvgs_head_decode_host: (boxes_out float32 [N, 4], scores_out float32 [N], classes_out int32 [N], index_out int32 [N], count) --
+    the bytes the kernels must write for `desc` -- computed on the CPU from the HOST array `head`: float32, float16, or uint16 holding
+    bfloat16 bits, addressed with the descriptor's strides."""
+    import numpy as np
+    lib = capi.load_library()
+    d = capi.HeadDesc.from_buffer_copy(desc)
+    want = {HEAD_F32: (np.float32,), HEAD_F16: (np.float16, np.uint16), HEAD_BF16: (np.uint16,)}.get(int(d.elem_type), ())
+    if not isinstance(head, np.ndarray) or (want and head.dtype not in [np.dtype(t) for t in want]):
+        raise ValueError("head must be a numpy array of the descriptor's element type (bfloat16 as uint16 bits)")
+    d.head = head.ctypes.data
+    n = max(int(d.max_candidates), 1)
+    bo, so = np.empty((n, 4), np.float32), np.empty((n,), np.float32)
+    ko, io = np.empty((n,), np.int32), np.empty((n,), np.int32)
+    co = C.c_int32(-1)
+    capi.check(lib.cvgs_head_decode_host(C.byref(d), bo.ctypes.data, so.ctypes.data, ko.ctypes.data, io.ctypes.data, C.addressof(co)))
+    return bo, so, ko, io, int(co.value)
+
+
 # ---- device-built warp tables: aligned crops from a detector's device-side landmarks (include/cvgs_hip_ext.h) ----------------
 WARP_FIT_SIMILARITY, WARP_FIT_AFFINE3 = capi.WARP_FIT_SIMILARITY, capi.WARP_FIT_AFFINE3
 

@@ -763,6 +763,81 @@ private:
     std::vector<std::shared_ptr<void>> owned_;
 };
 
+// ---- the network's raw head -> the candidates DeviceBoxSelect reads (engine extension: cvgs_head_decode, include/cvgs_hip_ext.h) --------
+// Best class, score, threshold and compaction on the device: two small kernels on the stream, the head read in place in fp32 / fp16 / bf16.
+//   cvGS::DeviceHeadDecode decode(8400);                                    // owns scratch and outputs for 8400 candidates
+//   decode.layout(d_head, CVGS_HEAD_BF16, 1, 8400, 80).threshold(0.25f);    // a [4 + 80, 8400] head: box 0..3, classes 4..83
+//   decode.feed(select);                                                    // select.candidates(...) and its count from the outputs
+//   decode.enqueue(stream); select.enqueue(stream);
+// The second constructor takes caller-owned buffers (scratch: cvgs_head_decode_scratch_bytes) and allocates nothing.
+class DeviceHeadDecode {
+public:
+    explicit DeviceHeadDecode(int maxCandidates, bool withIndices = true) {
+        init(maxCandidates);
+        const size_t sb = cvgs_head_decode_scratch_bytes(maxCandidates);
+        if (!sb) throw std::runtime_error("cvGS::DeviceHeadDecode: maxCandidates in [1, 65535]");
+        const size_t n = (size_t)maxCandidates;
+        d_.scratch = own(sb);
+        d_.boxes_out = static_cast<float*>(own(n * 4 * sizeof(float)));
+        d_.scores_out = static_cast<float*>(own(n * sizeof(float)));
+        d_.classes_out = static_cast<int32_t*>(own(n * sizeof(int32_t)));
+        d_.count_out = static_cast<int32_t*>(own(sizeof(int32_t)));
+        if (withIndices) d_.index_out = static_cast<int32_t*>(own(n * sizeof(int32_t)));
+    }
+    DeviceHeadDecode(int maxCandidates, void* scratch, float* boxesOut, float* scoresOut, int32_t* classesOut, int32_t* countOut, int32_t* indexOut = nullptr) {
+        init(maxCandidates);
+        d_.scratch = scratch; d_.boxes_out = boxesOut; d_.scores_out = scoresOut; d_.classes_out = classesOut; d_.count_out = countOut; d_.index_out = indexOut;
+    }
+    // where the head is (device pointer) and how it is laid out: attribute a of candidate i at element i * candStride + a * attrStride;
+    // [N, A]: (A, 1), [A, N]: (1, N).  objAttr == -1: no objectness value
+    DeviceHeadDecode& layout(const void* head, cvgs_head_elem elemType, int candStride, int attrStride, int numClasses, int boxAttr = 0, int classAttr = 4,
+                             int objAttr = -1) {
+        d_.head = head; d_.elem_type = (int32_t)elemType; d_.cand_stride = candStride; d_.attr_stride = attrStride; d_.num_classes = numClasses;
+        d_.box_attr = boxAttr; d_.class_attr = classAttr; d_.obj_attr = objAttr;
+        return *this;
+    }
+    DeviceHeadDecode& threshold(float score) { d_.score_threshold = score; return *this; }
+    void enqueue(const cv::cuda::Stream& stream) const { fk::detail::check_status(cvgs_head_decode(&d_, 1, cv::cuda::StreamAccessor::getStream(stream))); }
+    // several frames (the cameras of a tick, at most 16) in ONE call
+    static void enqueue(const cv::cuda::Stream& stream, const std::vector<const DeviceHeadDecode*>& jobs) {
+        std::vector<cvgs_head_desc> d;
+        d.reserve(jobs.size());
+        for (const DeviceHeadDecode* j : jobs) {
+            if (!j) throw std::runtime_error("cvGS::DeviceHeadDecode::enqueue: null DeviceHeadDecode");
+            d.push_back(j->d_);
+        }
+        fk::detail::check_status(cvgs_head_decode(d.data(), (int32_t)d.size(), cv::cuda::StreamAccessor::getStream(stream)));
+    }
+    // the selector reads this decoder's outputs: dense boxes (stride 4), scores, classes and the device count.  `format` is the head's
+    // box format; the selector's maxCandidates must be this decoder's
+    void feed(DeviceBoxSelect& select, cvgs_cand_format format = CVGS_CAND_XYXY_F32, bool classAware = true) const {
+        if (select.desc().max_candidates != d_.max_candidates) throw std::runtime_error("cvGS::DeviceHeadDecode::feed: the selector's maxCandidates differs");
+        select.candidates(d_.boxes_out, 4, d_.scores_out, 1, format, classAware ? d_.classes_out : nullptr, 1, d_.count_out);
+    }
+    const float* boxes() const { return d_.boxes_out; }
+    const float* scores() const { return d_.scores_out; }
+    const int32_t* classes() const { return d_.classes_out; }
+    const int32_t* indices() const { return d_.index_out; } // nullptr when built without
+    const int32_t* count() const { return d_.count_out; }
+    int maxCandidates() const { return d_.max_candidates; }
+    const cvgs_head_desc& desc() const { return d_; }
+private:
+    void init(int maxCandidates) {
+        std::memset(&d_, 0, sizeof(d_));
+        d_.struct_size = sizeof(d_);
+        d_.max_candidates = maxCandidates;
+        d_.elem_type = CVGS_HEAD_F32; d_.cand_stride = 1; d_.attr_stride = 1; d_.num_classes = 1; d_.class_attr = 4; d_.obj_attr = -1;
+    }
+    void* own(size_t bytes) {
+        void* p = nullptr;
+        fk::hip_check(hipMalloc(&p, bytes), "hipMalloc(head decode)");
+        owned_.push_back(std::shared_ptr<void>(p, [](void* q) { (void)hipFree(q); }));
+        return p;
+    }
+    cvgs_head_desc d_;
+    std::vector<std::shared_ptr<void>> owned_;
+};
+
 // resize<T, INTER_LINEAR | INTER_AREA, AR>(deviceCrops, backgroundValue): the batched read over the device-built table -- maxBoxes planes of the size and
 // aspect-ratio mode of the last update() (AR must be that mode), invalid boxes and the AR padding take backgroundValue.  fk::executeDivergentBatch
 // keeps refusing device tables (it selects planes on the host).

@@ -3,7 +3,8 @@
  * descriptor queue (cvgs_queue_*: an opt-in submission path, frozen since round 5), the device-side arrival flags of the sharded
  * batched-crop path (cvgs_exchange_*: BASELINE cfg #5, SURVEY.md 8e option 2) and plane tables built on the device from a detector's
  * device-side boxes (cvgs_plane_tables_from_boxes) and warp tables fitted on the device to its device-side landmarks
- * (cvgs_warp_tables_from_points).  The drop-in boundary -- what replaces
+ * (cvgs_warp_tables_from_points), device-side box selection (cvgs_boxes_select) and the decoding of a network's raw head into its
+ * candidates (cvgs_head_decode).  The drop-in boundary -- what replaces
  * fk::executeOperations and fk::CircularTensor (reference include/cvGPUSpeedup.cuh:464-627) -- is include/cvgs_hip.h alone; nothing
  * there depends on this file.  Same conventions: plain C, asynchronous on the given stream, 0 or a negative cvgs_status.
  */
@@ -340,6 +341,86 @@ typedef struct cvgs_box_select_desc {
 size_t cvgs_boxes_select_scratch_bytes(int32_t max_candidates, int32_t pre_nms_k);
 int cvgs_boxes_select(const cvgs_box_select_desc* descs, int32_t n, cvgs_stream_t stream); /* n = 1..CVGS_SELECT_MAX_FRAMES frames, one call */
 int cvgs_boxes_select_host(const cvgs_box_select_desc* desc, void* boxes_out, int32_t* count_out, float* scores_out, int32_t* index_out);
+
+/* ---- a detector's raw head -> the candidates cvgs_boxes_select reads ---------------------------------------------------------------------
+ * What sits between a network's output tensor and cvgs_boxes_select.  Select reads four contiguous fp32 coordinates, one fp32 score and
+ * one int32 class per candidate; exported heads offer none of that: YOLOv8 / v9 / v11 emit [4 + C, N] (channel-major), YOLOv5-style heads
+ * [N, 5 + C] with an objectness value, both with C class scores per candidate and often in fp16 / bf16.  cvgs_head_decode enqueues TWO
+ * small kernels on `stream` (csrc/k_head.hip: score, then compact) for up to 16 frames and nothing else: no allocation, no staging, no
+ * copy, no synchronisation, so the call can be captured between the network and cvgs_boxes_select.  It reads the head in place through
+ * two strides, reduces the class scores to (score, class), and hands select ONLY the candidates over the threshold, in candidate order,
+ * with their number on the device: boxes_out / scores_out / classes_out / count_out are by construction a valid boxes (box_stride 4) /
+ * scores (score_stride 1) / classes (class_stride 1) / count of a cvgs_box_select_desc with the same max_candidates.  The box format stays
+ * the detector's (XYXY or CXCYWH): select converts and transforms as it does for any candidates.  Its cost: see README.md.
+ *
+ * Attribute a of candidate i is element head[i * cand_stride + a * attr_stride] (indexed in size_t, in elements of elem_type): a [N, A]
+ * tensor is (A, 1), an [A, N] tensor is (1, N), padded rows or channels take a larger stride.  The four coordinates are the attributes
+ * box_attr .. box_attr + 3, the class scores class_attr .. class_attr + num_classes - 1, the objectness value obj_attr (or -1: none).
+ *
+ * THE CONTRACT.  One text for the kernels and for cvgs_head_decode_host (csrc/cvgs_geometry.h: head_widen_f16 / head_widen_bf16,
+ * head_best_step, head_best_wins, head_score, head_member), compiled with -ffp-contract=off, so the device writes the host entry's bytes.
+ * Per frame, for every candidate i < max_candidates:
+ *   1. WIDENING.  Every value read is widened to fp32, exactly: CVGS_HEAD_BF16 is the top 16 bits of an fp32; CVGS_HEAD_F16 widens exactly
+ *      (subnormals included); CVGS_HEAD_F32 is read as it is.
+ *   2. BEST CLASS.  best = -inf, cls = 0; for c = 0 .. num_classes - 1 in order, with v the class score of c: if (v > best) { best = v;
+ *      cls = c; }.  A NaN never wins; among scores that compare equal the lowest class index wins (-0.0f equals 0.0f); best carries the
+ *      winner's bits.  EQUIVALENT PARALLEL FORM (a wave reduction may use it): the maximum under "(v, c) beats (b, cb) iff (v > b) ||
+ *      (v == b && c < cb)" over the non-NaN entries, with identity (-inf, 0).
+ *   3. SCORE.  score = best; with obj_attr >= 0, score = obj * best: one fp32 multiplication, rounded once.
+ *   4. MEMBERSHIP.  i is a MEMBER iff score >= score_threshold and none of its four widened coordinates is NaN.  A NaN score (NaN
+ *      objectness, inf * 0) fails the first test.
+ *   5. COMPACTION.  Members are compacted in candidate-index order.  The k-th member, counted from 0, is written as boxes_out[k] = its four
+ *      widened coordinates as read, scores_out[k] = its score, classes_out[k] = its cls, index_out[k] = its candidate index; count_out =
+ *      the number of members.
+ *   6. EVERY element is written on every call: elements at or beyond count_out get (0, 0, 0, 0), 0.0f, 0 and -1.
+ * CONSEQUENCES.  No NaN is ever stored.  There is no division and no transcendental function; apart from the multiplication of step 3
+ * every step is a comparison or a move.  Because order is preserved, select's tie rule ("lower index first") means the same on the
+ * compacted list as on the dense one: cvgs_boxes_select over the decoder's outputs, with the same score_threshold, returns exactly what
+ * it returns over the dense per-candidate (score, class) arrays -- only its index_out differs, and it maps back to candidate indices
+ * through the decoder's index_out (which is what a caller gathers landmarks or masks of kept candidates with).
+ * OUT OF SCOPE.  Heads are expected to hold probabilities (exported graphs apply the sigmoid themselves): there is no sigmoid / exp, no
+ * anchor or DFL decoding, no device `count` INPUT, and no gather of landmarks of kept candidates.
+ * HOW (csrc/k_head.hip): both launches have the grid (256 candidates per workgroup, frame).  The score launch computes steps 1-4 for every
+ * candidate and stores its score, class and member flag, and the tile's member count (ballot + popcount, the four wave totals through LDS),
+ * in `scratch`.  It has two forms, chosen on the host by stride: attr_stride != 1 (and any stride pair): one lane per candidate walking the
+ * classes, so that with cand_stride == 1 a wave's load of one channel is one contiguous span; attr_stride == 1: a group of 4 .. 64 lanes
+ * per candidate reads consecutive attributes and reduces under the parallel form of step 2.  The compact launch has every workgroup sum
+ * the counts of the tiles in front of it (at most 256), pack its own members behind them, read the coordinates of members only, and zero
+ * the part of its own range that lies at or beyond the total.  No atomic, no workgroup waits for another, nothing depends on the order in
+ * which workgroups run.  `scratch` (device, 8-byte aligned, cvgs_head_decode_scratch_bytes(max_candidates) bytes -- 0 for an argument out
+ * of range) belongs to the call from its enqueue to the end of the compact launch; its contents before and after are unspecified.
+ * Validation happens completely on the host before the first HIP call (a machine without a GPU can test it): null descriptors, null
+ * head / scratch / boxes_out / scores_out / classes_out / count_out, struct_size, flags, reserved, n outside 1..16, a bad elem_type,
+ * max_candidates outside 1..65535, cand_stride or attr_stride < 1, num_classes outside 1..4096, an attribute index outside 0..8191
+ * (box_attr + 3, class_attr + num_classes - 1, obj_attr -- which may also be -1), misaligned pointers (head: its element size; outputs:
+ * 4 bytes; scratch: 8), a NaN score_threshold (-inf is allowed), output or scratch buffers of one call that overlap -> CVGS_ERR_INVALID.
+ *   cvgs_head_decode_host  the same descriptor with a HOST `head`; desc's scratch and output pointers are ignored and the results go to
+ *                          boxes_out (float[N][4]), scores_out, classes_out, index_out (optional) and count_out.  Runs the shared text on
+ *                          the CPU and writes the bytes the kernels must write; makes no HIP call.
+ * No reference counterpart.                                                                                                          */
+typedef enum cvgs_head_elem { CVGS_HEAD_F32 = 0, CVGS_HEAD_F16 = 1, CVGS_HEAD_BF16 = 2 } cvgs_head_elem;
+#define CVGS_HEAD_MAX_FRAMES 16
+#define CVGS_HEAD_MAX_CLASSES 4096
+#define CVGS_HEAD_MAX_ATTR 8191
+typedef struct cvgs_head_desc {
+    uint32_t struct_size, flags;          /* sizeof(cvgs_head_desc); flags: must be 0 */
+    const void* head;                     /* device: attribute a of candidate i at element i * cand_stride + a * attr_stride */
+    int32_t elem_type, max_candidates;    /* cvgs_head_elem; N: 1..65535 */
+    int32_t cand_stride, attr_stride;     /* in elements: >= 1 */
+    int32_t box_attr, obj_attr;           /* the first of four coordinate attributes; the objectness attribute or -1 */
+    int32_t class_attr, num_classes;      /* the first of num_classes class-score attributes; 1..CVGS_HEAD_MAX_CLASSES */
+    float score_threshold;                /* not NaN; -inf keeps every candidate without a NaN coordinate or score */
+    int32_t reserved;                     /* 0 */
+    void* scratch;                        /* device, 8-byte aligned, cvgs_head_decode_scratch_bytes(max_candidates) */
+    float* boxes_out;                     /* device float[N][4] */
+    float* scores_out;                    /* device float[N] */
+    int32_t* classes_out;                 /* device int32[N] */
+    int32_t* index_out;                   /* device int32[N], or NULL */
+    int32_t* count_out;                   /* device int32 */
+} cvgs_head_desc;
+size_t cvgs_head_decode_scratch_bytes(int32_t max_candidates);
+int cvgs_head_decode(const cvgs_head_desc* descs, int32_t n, cvgs_stream_t stream); /* n = 1..CVGS_HEAD_MAX_FRAMES frames, one call */
+int cvgs_head_decode_host(const cvgs_head_desc* desc, float* boxes_out, float* scores_out, int32_t* classes_out, int32_t* index_out, int32_t* count_out);
 
 #ifdef __cplusplus
 }

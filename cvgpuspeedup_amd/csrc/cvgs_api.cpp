@@ -1302,7 +1302,7 @@ bool chains_independent(const cvgs_chain_desc* const* chains, int n) {
     return true;
 }
 
-// A TICK: n chains of one shape in ONE launch.  Five kernel families take one:
+// A TICK: n chains of one shape in ONE launch.  Six kernel families take one:
 //   pointwise  per-pixel reads of u8 planes of ONE size, host descriptors, a dense fp32 target per chain (round 6; the reference's batched per-pixel
 //              chains, tests/batchread/test_batchread_x_write3D.cu:92-96: BATCH crops -> convertTo -> subtract -> divide -> tensor, launch-bound
 //              at 4 us for 50 crops of 60 x 120)
@@ -1311,8 +1311,12 @@ bool chains_independent(const cvgs_chain_desc* const* chains, int n) {
 //              K1's three carriers -- device tables included; a captured AREA tick is one kernel node in stream order (overlap and merge stay K1's)
 //   yuv_area   the INTER_AREA resize of 8-bit NV12 / NV21 surfaces into a planar fp32 / fp16 / bf16 tensor (k_yuv_area.hip: every chain
 //              try_yuv_area_fast takes), with the same three carriers and the same place in a captured stream as `area`
+//   warp       the affine / perspective warp of u8 C3 / C4 pixels into a planar fp32 / fp16 / bf16 tensor (k_warp.hip: every planar chain try_warp_fast
+//              takes, one target size for all planes), with TWO carriers: the callers' device warp tables (cvgs_warp_tables_from_points), or host
+//              descriptors of at most kManyInlineWarp planes in the kernel arguments -- no staged host table: more planes run chain by chain.  A
+//              captured warp tick is one kernel node in stream order, as `area`
 // plan_tick answers from the descriptors alone; what only the LOWERED chains show is found by launch_tick, which then gives up before anything is enqueued.
-enum class TickFamily { none, pointwise, k1, k4, area, yuv_area };
+enum class TickFamily { none, pointwise, k1, k4, area, yuv_area, warp };
 struct TickPlan {
     TickFamily family = TickFamily::none;
     TickCarrier carrier = TickCarrier::kernarg;
@@ -1335,17 +1339,25 @@ TickPlan plan_tick(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream)
                 : c0.read.kind == CVGS_READ_RESIZE_LINEAR ? TickFamily::k1
                 : c0.read.kind == CVGS_READ_NV12_RESIZE_LINEAR ? TickFamily::k4
                 : c0.read.kind == CVGS_READ_RESIZE_AREA ? TickFamily::area
-                : c0.read.kind == CVGS_READ_NV12_RESIZE_AREA ? TickFamily::yuv_area : TickFamily::none;
+                : c0.read.kind == CVGS_READ_NV12_RESIZE_AREA ? TickFamily::yuv_area
+                : is_warp(c0.read.kind) ? TickFamily::warp : TickFamily::none;
     if (plan.family == TickFamily::none) return refused("not fused: no tick kernel for this read kind");
-    const bool pw = plan.family == TickFamily::pointwise;
+    const bool pw = plan.family == TickFamily::pointwise, warp = plan.family == TickFamily::warp;
     const bool tables = (c0.read.flags & CVGS_READ_FLAG_TABLE_ON_DEVICE) != 0;
     const bool any_area = plan.family == TickFamily::area || plan.family == TickFamily::yuv_area; // (lower() admits device tables of NV12 / NV21 only for the surface kind)
-    if (tables && plan.family != TickFamily::k1 && !any_area) return refused("not fused: device tables outside K1 and AREA"); // per-pixel reads and K4's per-plane preconditions want the planes on the host
+    if (tables && plan.family != TickFamily::k1 && !any_area && !warp) return refused("not fused: device tables outside K1, AREA and the warps"); // per-pixel reads and K4's per-plane preconditions want the planes on the host
     int min_batch = 1;
     const cvgs_chain_desc* ptrs[CVGS_MAX_CHAINS];
     for (int i = 0; i < n; ++i) { // one shape (same_shape: kind, program, target extent), one descriptor form; the planes counted
         const cvgs_chain_desc& c = chains[i];
         const int wk = c.write.kind;
+        if (warp) { // what the warp tick does not take is said by name: the one-by-one path serves all of it
+            if (c.read.kind != c0.read.kind) return refused("not fused: the chains differ in shape, target kind or descriptor form");
+            if (c.flags & CVGS_CHAIN_FORCE_GENERIC) return refused("not fused: CVGS_CHAIN_FORCE_GENERIC asks for the interpreted warp kernel");
+            if (c.read.warp_dst_sizes) return refused("not fused: warp chains with per-plane target sizes (warp_dst_sizes)");
+            if (wk != CVGS_WRITE_TENSOR_SPLIT && wk != CVGS_WRITE_TENSOR_T_SPLIT) return refused("not fused: the warp tick writes planar tensors (TENSOR_SPLIT / TENSOR_T_SPLIT)");
+            if (c.read.src_type != CVGS_MAKETYPE(CVGS_DEPTH_8U, 3) && c.read.src_type != CVGS_MAKETYPE(CVGS_DEPTH_8U, 4)) return refused("not fused: the warp tick reads 8UC3 / 8UC4 sources");
+        }
         if ((c.flags & (pw ? CVGS_CHAIN_FORCE_GENERIC | CVGS_CHAIN_NO_THREAD_FUSION : CVGS_CHAIN_FORCE_GENERIC)) ||
             (wk != CVGS_WRITE_TENSOR_SPLIT && wk != CVGS_WRITE_TENSOR_T_SPLIT && !(pw && wk == CVGS_WRITE_PIXEL_3D)) || !same_shape(c0, c) ||
             ((c.read.flags ^ c0.read.flags) & CVGS_READ_FLAG_TABLE_ON_DEVICE) != 0)
@@ -1365,6 +1377,8 @@ TickPlan plan_tick(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream)
                         is_yuv422(c0.read.yuv_layout) || is_yuv444(c0.read.yuv_layout));
     const bool ya_il = plan.family == TickFamily::yuv_area && (c0.read.yuv_layout == CVGS_YUV_NV12 || c0.read.yuv_layout == CVGS_YUV_NV21);
     if (tables) plan.carrier = TickCarrier::device_tables;
+    else if (warp && plan.total_planes > (size_t)cvgs::kManyInlineWarp) return refused("not fused: more host-described warp planes than the tick's argument block holds"); // (no staged host table for warps)
+    else if (warp) plan.carrier = TickCarrier::kernarg;
     else if ((pw || (inline_ok && (k1_u8 || k4_il || ya_il))) && plan.total_planes <= (size_t)cvgs::kManyInlineLarge) plan.carrier = TickCarrier::kernarg;
     else if (pw) return refused("not fused: too many planes for a pointwise tick"); // (the pointwise tick has no table form)
     else plan.carrier = TickCarrier::host_table;
@@ -1389,6 +1403,7 @@ bool tick_kernel_takes(TickFamily family, const Lowered& L0, hipStream_t stream)
     if (family == TickFamily::k4) return launch_yuv_resize(probe, nullptr, 0, 1 << 30, pctx, true, nullptr) == 1; // K4 checks its planes on the host
     if (family == TickFamily::area) return !L0.uses_64f && launch_area_many(probe, nullptr, 0, pctx, true, nullptr) == 1; // (CV_64F values: dispatch's refusal, chain by chain)
     if (family == TickFamily::yuv_area) return !L0.uses_64f && launch_yuv_area_many(probe, nullptr, 0, pctx, true, nullptr) == 1; // (no per-plane host preconditions: byte loads, odd sizes)
+    if (family == TickFamily::warp) return !L0.uses_64f && launch_warp_many(probe, nullptr, 0, (const WarpPlane*)probe.read.table, pctx, true, nullptr) == 1;
     return launch_k1(probe, nullptr, 0, pctx, true, nullptr) == 1;
 }
 // Can lowered chain L ride in the family's tick with chain 0 (L0)?
@@ -1414,7 +1429,7 @@ bool tick_chain_fits(TickFamily family, const Lowered& L, const Lowered& L0) {
 // needs HIP or the chain descriptors.  No stream, no event, nothing for an eager launch.
 
 // what the tick reads and writes, from the chains' own statements (chains_independent reads the same fields)
-void tick_footprint(const cvgs_chain_desc* chains, int n, const ManySeg* segs, TickFootprint& fp) {
+void tick_footprint(const cvgs_chain_desc* chains, int n, const ManySeg* segs, size_t entry_bytes, TickFootprint& fp) { // entry_bytes: one table entry (PlaneParams, WarpPlane)
     fp.clear();
     for (int i = 0; i < n; ++i) {
         const cvgs_chain_desc& c = chains[i];
@@ -1424,7 +1439,7 @@ void tick_footprint(const cvgs_chain_desc* chains, int n, const ManySeg* segs, T
         for (int m = 0; m < c.write.n_mirrors && c.write.mirrors; ++m)
             fp.write(c.write.mirrors[m], c.write.mirrors[m] ? (const uint8_t*)c.write.mirrors[m] + (out.hi - out.lo) : nullptr);
         fp.read(c.read.table_src_lo, c.read.table_src_hi); // (vouched but unstated: null, i.e. unknown)
-        fp.read(segs[i].table, segs[i].table ? segs[i].table + segs[i].batch : nullptr);
+        fp.read(segs[i].table, segs[i].table ? (const uint8_t*)segs[i].table + (size_t)segs[i].batch * entry_bytes : nullptr);
     }
 }
 
@@ -1494,10 +1509,14 @@ void key_of(const TickLaunchRecord& r, std::vector<unsigned char>& out) {
 }
 
 // The planned tick: 1 launched / 0 not a fused launch after all (nothing was enqueued, and `table` has given back what it took) / < 0 error.
-int launch_tick(const cvgs_chain_desc* chains, int32_t n, const TickPlan& plan, hipStream_t stream) {
+int launch_tick(const cvgs_chain_desc* chains, int32_t n, const TickPlan& plan, hipStream_t stream, const char** why) {
     const bool pw = plan.family == TickFamily::pointwise, k4 = plan.family == TickFamily::k4, area = plan.family == TickFamily::area, yuv_area = plan.family == TickFamily::yuv_area;
+    const bool warp = plan.family == TickFamily::warp;
     ManySeg segs[CVGS_MAX_CHAINS];
     TickTable table;
+    // the warp tick's kernel-argument carrier: every chain's WarpPlanes, in chain order (device tables: nothing is held; TickTable carries PlaneParams)
+    static thread_local std::vector<WarpPlane> warp_planes;
+    warp_planes.clear();
     Lowered L0; // the shared read / program / write arguments come from chain 0
     for (int i = 0; i < n; ++i) { // (one chain at a time: a Lowered holds 320 inline planes)
         Lowered Li;
@@ -1505,12 +1524,23 @@ int launch_tick(const cvgs_chain_desc* chains, int32_t n, const TickPlan& plan, 
         int rc = lower(&chains[i], false, L);
         if (rc) return rc; // nothing enqueued yet
         if (i == 0) {
-            if (!pw && !tick_kernel_takes(plan.family, L0, stream)) return 0; // (the pointwise kernel is asked below, with the planes it will get)
-            rc = table.begin(plan.carrier, plan.total_planes * sizeof(PlaneParams) + 16 * (size_t)n, stream);
+            if (!pw && !tick_kernel_takes(plan.family, L0, stream)) { // (the pointwise kernel is asked below, with the planes it will get)
+                if (warp) *why = "not fused: the fast warp kernel does not take this chain (CV_64F or integer-typed arithmetic, a cast inside the program, or a target type other than fp32 / fp16 / bf16)";
+                return 0;
+            }
+            if (!warp) rc = table.begin(plan.carrier, plan.total_planes * sizeof(PlaneParams) + 16 * (size_t)n, stream);
             if (rc) return rc;
         }
         if (!tick_chain_fits(plan.family, L, L0)) return 0;
-        segs[i] = ManySeg{table.put(L), L.args.write.data, L.args.read.batch, L.args.read.used};
+        const PlaneParams* at;
+        if (!warp) at = table.put(L);
+        else if (plan.carrier == TickCarrier::device_tables) at = L.args.read.table; // the chain's own WarpPlane table
+        else { // the chain's first index into the block's planes
+            if ((int)L.warp_planes.size() != L.args.read.batch || warp_planes.size() + L.warp_planes.size() > (size_t)cvgs::kManyInlineWarp) return fail(CVGS_ERR_INVALID, "inline warp tick: more planes than counted");
+            at = (const PlaneParams*)(uintptr_t)warp_planes.size();
+            warp_planes.insert(warp_planes.end(), L.warp_planes.data(), L.warp_planes.data() + L.warp_planes.size());
+        }
+        segs[i] = ManySeg{at, L.args.write.data, L.args.read.batch, L.args.read.used};
     }
     ChainArgs c = L0.args;
     c.read.batch = plan.max_batch;
@@ -1538,7 +1568,7 @@ int launch_tick(const cvgs_chain_desc* chains, int32_t n, const TickPlan& plan, 
                                        (int)std::min<int64_t>(std::max<int64_t>(env_int("CVGS_TICK_MERGE_MAX_CHAINS", kTickMergeMaxChains), 2), kTickMergeMaxChains),
                                        kTickOverlapMaxPixels};
     const TickBegin how = capture.begin(
-        facts, cfg, [&](TickFootprint& fp) { tick_footprint(chains, n, segs, fp); },
+        facts, cfg, [&](TickFootprint& fp) { tick_footprint(chains, n, segs, warp ? sizeof(WarpPlane) : sizeof(PlaneParams), fp); },
         [&](TickLaunchRecord& rec, std::vector<unsigned char>& key) -> const void* { // what the tick would launch: the launch site builds its arguments and enqueues nothing
             LaunchCtx probe(stream);
             probe.segs = segs;
@@ -1552,7 +1582,8 @@ int launch_tick(const cvgs_chain_desc* chains, int32_t n, const TickPlan& plan, 
     if (how != TickBegin::merged) {
         rc = k4 ? launch_yuv_resize(c, table.planes(), table.n_planes(), 1 << 30, ctx, false, nullptr)
            : area ? launch_area_many(c, table.planes(), table.n_planes(), ctx, false, nullptr)
-           : yuv_area ? launch_yuv_area_many(c, table.planes(), table.n_planes(), ctx, false, nullptr) : launch_k1(c, table.planes(), table.n_planes(), ctx, false, nullptr);
+           : yuv_area ? launch_yuv_area_many(c, table.planes(), table.n_planes(), ctx, false, nullptr)
+           : warp ? launch_warp_many(c, warp_planes.data(), (int)warp_planes.size(), (const WarpPlane*)c.read.table, ctx, false, nullptr) : launch_k1(c, table.planes(), table.n_planes(), ctx, false, nullptr);
         if (rc != 1) {
             capture.abandon();
             return fail(CVGS_ERR_HIP, "fused kernel launch failed");
@@ -1565,8 +1596,9 @@ int launch_tick(const cvgs_chain_desc* chains, int32_t n, const TickPlan& plan, 
 
 int execute_many(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream) {
     const TickPlan plan = plan_tick(chains, n, stream);
+    const char* why = plan.why; // an un-fused tick says why: plan_tick from the descriptors, launch_tick from the lowered chains
     if (plan.family != TickFamily::none) {
-        const int rc = launch_tick(chains, n, plan, stream);
+        const int rc = launch_tick(chains, n, plan, stream, &why);
         if (rc) return rc < 0 ? rc : CVGS_OK;
     }
     for (int i = 0; i < n; ++i) {
@@ -1577,7 +1609,7 @@ int execute_many(const cvgs_chain_desc* chains, int32_t n, hipStream_t stream) {
         if (rc) return rc;
     }
     g_tick_note = TickNote();
-    g_tick_note.plain = plan.why ? plan.why : "not fused: the tick kernel does not take these chains"; // (an un-fused tick is not silent)
+    g_tick_note.plain = why ? why : "not fused: the tick kernel does not take these chains"; // (an un-fused tick is not silent)
     return CVGS_OK;
 }
 

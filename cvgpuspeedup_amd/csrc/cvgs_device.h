@@ -4,6 +4,7 @@
 // launch with no side uploads.  Large crop lists use a device-resident plane table instead.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include <string>
@@ -279,6 +280,26 @@ static constexpr int kInlineWarp = 52; // planes whose WarpPlane travels in the 
 // interpreted warp kernel: `planes` = host array of n (inline when n <= kInlineWarp), else `dev_table` (device copy)
 int launch_warp(const ChainArgs& c, const WarpPlane* planes, int n, const WarpPlane* dev_table, uint32_t chain_flags, void* stream,
                 bool dry_run, LaunchInfo* info);
+// The warp tick's argument block for host-described chains: the WarpPlanes of ALL chains behind the segment block (ManySeg::table holds the
+// chain's first index into `planes`; ManySeg::table of a device-table tick is the address of a WarpPlane table).  A WarpPlane is 64 bytes
+// against PlaneParams' 48, so the block is the warp tick's own; ONE capacity: 16 frames of 16 items, a 20 KB block (the host pays for the
+// declared bytes: KernArgsManyInline above), inside what the largest PlaneParams block already occupies.
+static constexpr int kManyInlineWarp = 256;
+template <int N>
+struct WarpArgsManyInline {
+    ChainArgs c;
+    ManySeg seg[CVGS_MAX_CHAINS];
+    WarpPlane planes[N];
+};
+static_assert(kManyInlineWarp >= 256 && sizeof(WarpArgsManyInline<kManyInlineWarp>) <= sizeof(KernArgsManyInline<kManyInlineLarge>),
+              "inline warp tick block: at least 256 planes, no larger than the largest inline tick block");
+static_assert(offsetof(WarpArgsManyInline<kManyInlineWarp>, seg) == offsetof(KernArgsMany, seg) && offsetof(WarpArgsManyInline<kManyInlineWarp>, planes) % 8 == 0,
+              "inline warp tick block: the segments where KernArgsMany has them, the planes 8-byte aligned");
+// The fast warp kernel for the chains of a cvgs_execute_many launch (ctx.segs; c.read.batch is the largest batch; planar tensor targets):
+// dev_table != nullptr: every segment's table is the device address of the chain's own WarpPlane table; nullptr: `planes` holds the planes
+// of all chains (at most kManyInlineWarp) and travels in the kernel arguments.  There is no staged host table for warps.
+// 1 launched (dry run: would launch) / 0 not a chain the fast kernel takes / < 0 error
+int launch_warp_many(const ChainArgs& c, const WarpPlane* planes, int n_planes, const WarpPlane* dev_table, LaunchCtx& ctx, bool dry_run, LaunchInfo* info);
 
 // INTER_AREA resize (k_area.hip): CVGS_READ_RESIZE_AREA chains, planes as for the bilinear resize (inline up to CVGS_KERNARG_PLANES,
 // else c.read.table).  The fast kernels (u8 C3/C4 -> static program -> planar fp32 / fp16 / bf16 tensor) or the interpreted one; 0 or a HIP error code

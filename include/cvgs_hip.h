@@ -450,10 +450,13 @@ int cvgs_execute(const cvgs_chain_desc* chain, cvgs_stream_t stream);
  * fp32 / fp16 tensor (the K1 / K4 shapes) -- or, since round 6, a per-pixel read of 8U planes of ONE size (host descriptors) through an fp32 program into a
  * dense fp32 tensor / packed pixels (the reference's batched pointwise chains, tests/batchread/test_batchread_x_write3D.cu:92-96), or an INTER_AREA
  * resize of 8U pixels with 3 / 4 channels, or of 8-bit NV12 / NV21 surfaces or crops of them, into a planar fp32 / fp16 / bf16 tensor
- * (CVGS_READ_RESIZE_AREA, CVGS_READ_NV12_RESIZE_AREA; host descriptors or device tables) --, and that agree in
+ * (CVGS_READ_RESIZE_AREA, CVGS_READ_NV12_RESIZE_AREA; host descriptors or device tables), or an affine / perspective warp of 8U pixels
+ * with 3 / 4 channels into a planar fp32 / fp16 / bf16 tensor (CVGS_READ_WARP_AFFINE / _PERSPECTIVE with one target size, no
+ * warp_dst_sizes; device warp tables, or host descriptors of at most 256 planes in all, which travel in the kernel arguments -- more run
+ * one by one) --, and that agree in
  * everything except read.src / batch / used_planes and write.data / planes (same source type, target size,
  * aspect-ratio mode, background, YUV range / primaries / layout, pointwise stages and operands, write kind and type), are
- * fused into ONE launch of the K1 (or K4, pointwise, AREA) kernel: grid z = chain, grid y = crop.  Results are bit-identical to n_chains separate cvgs_execute calls (same
+ * fused into ONE launch of the K1 (or K4, pointwise, AREA, warp) kernel: grid z = chain, grid y = crop.  Results are bit-identical to n_chains separate cvgs_execute calls (same
  * kernel code; tests/test_gpu_many.py).  Any other set of chains is executed one by one, in order -- and so is a set whose
  * chains are NOT independent (two chains write overlapping bytes, or a source view of one -- chroma rows of a 4:2:0
  * surface included -- lies inside another's output: fused chains run concurrently; chains whose plane table lives on the device are checked

@@ -233,7 +233,11 @@ int cvgs_plane_tables_from_boxes(const cvgs_box_table_desc* descs, int32_t n, cv
  * warp_matrices == NULL and warp_dst_sizes == NULL (either non-null: CVGS_ERR_INVALID).  The launch reads the caller's table where a
  * host-described batch beyond the inline limit reads an uploaded copy: nothing is staged, and cvgs_kernel_name gives the names of
  * host-described chains of the same shape (a CV_64F program: the table variant, which host-described batches of more than 8 planes get).
- * CV_64F sources are served through host descriptors only.  cvgs_execute_many runs such chains one by one (as every warp); the descriptor
+ * CV_64F sources are served through host descriptors only.  cvgs_execute_many fuses independent chains of ONE shape over such tables --
+ * 8UC3 / 8UC4 frames, one target size, a cast-free program, planar fp32 / fp16 / bf16 tensors -- into ONE launch (the warp tick: grid
+ * z = chain, bit-identical to one cvgs_execute per chain; the chains state the frame's byte range, read.table_src_lo / _hi, or vouch); the
+ * same holds for host-described warp chains of at most 256 planes in all, whose descriptors travel in the kernel arguments.  Everything
+ * else runs one by one, in order, and cvgs_last_error() says why ("not fused: ...").  The descriptor
  * queue and cvgs_circular_update refuse them (CVGS_ERR_UNSUPPORTED, before anything is enqueued).  The chain may state
  * read.table_src_lo / _hi = the whole frame's byte range.
  * Validation happens completely on the host before the first HIP call: null pointers, struct_size, flags, n outside 1..16, max_items

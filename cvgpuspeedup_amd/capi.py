@@ -161,6 +161,18 @@ class HeadDesc(C.Structure):
                 ("classes_out", C.c_void_p), ("index_out", C.c_void_p), ("count_out", C.c_void_p)]
 
 
+# the landmarks of kept detections -> the points of cvgs_warp_tables_from_points (include/cvgs_hip_ext.h: cvgs_points_gather)
+GATHER_MAX_FRAMES, GATHER_MAX_POINTS = 16, 64
+
+
+class PointGatherDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("head", C.c_void_p), ("elem_type", C.c_int32),
+                ("max_candidates", C.c_int32), ("cand_stride", C.c_int32), ("attr_stride", C.c_int32), ("point_attr", C.c_int32),
+                ("point_step", C.c_int32), ("n_points", C.c_int32), ("conf_offset", C.c_int32), ("max_out", C.c_int32),
+                ("reserved", C.c_int32), ("kept_index", C.c_void_p), ("kept_count", C.c_void_p), ("cand_index", C.c_void_p),
+                ("xform", C.c_float * 4), ("points_out", C.c_void_p), ("conf_out", C.c_void_p), ("source_out", C.c_void_p)]
+
+
 # every symbol include/cvgs_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("cvgs_abi_version", C.c_int, []),
@@ -208,6 +220,8 @@ SYMBOLS = [
     ("cvgs_head_decode_scratch_bytes", C.c_size_t, [C.c_int32]),
     ("cvgs_head_decode", C.c_int, [C.POINTER(HeadDesc), C.c_int32, C.c_void_p]),
     ("cvgs_head_decode_host", C.c_int, [C.POINTER(HeadDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("cvgs_points_gather", C.c_int, [C.POINTER(PointGatherDesc), C.c_int32, C.c_void_p]),
+    ("cvgs_points_gather_host", C.c_int, [C.POINTER(PointGatherDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cvgs_range_push", None, [C.c_char_p]),
     ("cvgs_range_pop", None, []),
 ]

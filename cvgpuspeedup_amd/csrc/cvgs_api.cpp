@@ -2332,6 +2332,91 @@ int cvgs_head_decode_host(const cvgs_head_desc* desc, float* boxes_out, float* s
     return CVGS_OK;
 }
 
+// The landmarks of kept detections -> the points of cvgs_warp_tables_from_points (include/cvgs_hip_ext.h: THE CONTRACT).  Everything is
+// validated here, on the host, before the first HIP call; the row's source, the element index, the widening and the mapping
+// (cvgs_geometry.h: gather_point) are one text for the kernel (k_gather.hip) and for cvgs_points_gather_host.
+namespace {
+// the outputs: the descriptor's (cvgs_points_gather) or the caller's in their place (cvgs_points_gather_host)
+int check_gather_desc(const cvgs_point_gather_desc& d, float* points_out, float* conf_out, int32_t* source_out, GatherFrame& f) {
+    if (d.struct_size != sizeof(cvgs_point_gather_desc)) return fail(CVGS_ERR_INVALID, "cvgs_point_gather_desc size mismatch (ABI)");
+    if (d.flags) return fail(CVGS_ERR_INVALID, "points_gather: flags must be 0");
+    if (d.reserved) return fail(CVGS_ERR_INVALID, "points_gather: reserved must be 0");
+    if (d.elem_type != CVGS_HEAD_F32 && d.elem_type != CVGS_HEAD_F16 && d.elem_type != CVGS_HEAD_BF16) return fail(CVGS_ERR_INVALID, "points_gather: bad elem_type");
+    if (d.max_candidates < 1 || d.max_candidates > 65535) return fail(CVGS_ERR_INVALID, "points_gather: max_candidates must be in [1, 65535]");
+    if (d.max_out < 1 || d.max_out > 65535) return fail(CVGS_ERR_INVALID, "points_gather: max_out must be in [1, 65535]");
+    if (!d.head) return fail(CVGS_ERR_INVALID, "points_gather: head is null");
+    if (!d.kept_index) return fail(CVGS_ERR_INVALID, "points_gather: kept_index is null");
+    if (d.cand_stride < 1) return fail(CVGS_ERR_INVALID, "points_gather: cand_stride must be at least 1 element");
+    if (d.attr_stride < 1) return fail(CVGS_ERR_INVALID, "points_gather: attr_stride must be at least 1 element");
+    if (d.point_step < 2) return fail(CVGS_ERR_INVALID, "points_gather: point_step must be at least 2 attributes");
+    if (d.n_points < 1 || d.n_points > CVGS_GATHER_MAX_POINTS) return fail(CVGS_ERR_INVALID, "points_gather: n_points must be in [1, 64]");
+    if (d.conf_offset != -1 && (d.conf_offset < 2 || d.conf_offset >= d.point_step))
+        return fail(CVGS_ERR_INVALID, "points_gather: conf_offset must be -1 or lie in [2, point_step)");
+    if (!points_out) return fail(CVGS_ERR_INVALID, "points_gather: points_out is null");
+    if (conf_out && d.conf_offset == -1) return fail(CVGS_ERR_INVALID, "points_gather: conf_out given without a conf_offset");
+    if (!conf_out && d.conf_offset != -1) return fail(CVGS_ERR_INVALID, "points_gather: conf_offset given without conf_out");
+    // the last attribute addressed: y, or the confidence, of the last point (64 bits: point_step has no upper bound of its own)
+    const int64_t last = (int64_t)d.point_attr + (int64_t)(d.n_points - 1) * (int64_t)d.point_step + (d.conf_offset > 1 ? d.conf_offset : 1);
+    if (d.point_attr < 0 || last > CVGS_HEAD_MAX_ATTR) return fail(CVGS_ERR_INVALID, "points_gather: the attributes of the points must lie in [0, 8191]");
+    if ((uintptr_t)d.head & (head_elem_bytes(d.elem_type) - 1)) return fail(CVGS_ERR_INVALID, "points_gather: head needs the alignment of its element type");
+    if (((uintptr_t)d.kept_index | (uintptr_t)d.kept_count | (uintptr_t)d.cand_index | (uintptr_t)points_out | (uintptr_t)conf_out | (uintptr_t)source_out) & 3)
+        return fail(CVGS_ERR_INVALID, "points_gather: kept_index / kept_count / cand_index / points_out / conf_out / source_out need 4-byte alignment");
+    if (!fit_finite((double)d.xform[0]) || !fit_finite((double)d.xform[1]) || !(d.xform[0] > 0.0f) || !(d.xform[1] > 0.0f))
+        return fail(CVGS_ERR_INVALID, "points_gather: xform scales (sx, sy) must be finite and positive");
+    if (!fit_finite((double)d.xform[2]) || !fit_finite((double)d.xform[3])) return fail(CVGS_ERR_INVALID, "points_gather: xform offsets (ox, oy) must be finite");
+    f = GatherFrame{};
+    f.head = d.head; f.kept_index = d.kept_index; f.kept_count = d.kept_count; f.cand_index = d.cand_index;
+    f.points_out = points_out; f.conf_out = conf_out; f.source_out = source_out;
+    f.elem = d.elem_type; f.max_cand = d.max_candidates;
+    f.cand_stride = d.cand_stride; f.attr_stride = d.attr_stride;
+    f.point_attr = d.point_attr; f.point_step = d.point_step;
+    f.n_points = d.n_points; f.conf_offset = d.conf_offset;
+    f.max_out = d.max_out;
+    for (int k = 0; k < 4; ++k) f.xf[k] = d.xform[k];
+    return CVGS_OK;
+}
+} // namespace
+
+int cvgs_points_gather(const cvgs_point_gather_desc* descs, int32_t n, cvgs_stream_t stream) {
+    if (!descs) return fail(CVGS_ERR_INVALID, "points_gather: null descriptors");
+    if (n < 1 || n > CVGS_GATHER_MAX_FRAMES) return fail(CVGS_ERR_INVALID, "points_gather: n must be in [1, 16]");
+    GatherFrame frames[CVGS_GATHER_MAX_FRAMES];
+    ByteRange outs[3 * CVGS_GATHER_MAX_FRAMES];
+    int n_outs = 0;
+    for (int i = 0; i < n; ++i) {
+        const int rc = check_gather_desc(descs[i], descs[i].points_out, descs[i].conf_out, descs[i].source_out, frames[i]);
+        if (rc) return rc;
+        const GatherFrame& f = frames[i];
+        const size_t items = (size_t)f.max_out * (size_t)f.n_points;
+        outs[n_outs++] = ByteRange{(const uint8_t*)f.points_out, (const uint8_t*)f.points_out + items * 2 * sizeof(float)};
+        if (f.conf_out) outs[n_outs++] = ByteRange{(const uint8_t*)f.conf_out, (const uint8_t*)f.conf_out + items * sizeof(float)};
+        if (f.source_out) outs[n_outs++] = ByteRange{(const uint8_t*)f.source_out, (const uint8_t*)f.source_out + (size_t)f.max_out * sizeof(int32_t)};
+    }
+    for (int i = 0; i < n_outs; ++i)
+        for (int j = 0; j < i; ++j)
+            if (outs[i].lo < outs[j].hi && outs[j].lo < outs[i].hi) return fail(CVGS_ERR_INVALID, "points_gather: the output buffers of one call overlap");
+    const int e = launch_gather(frames, n, stream);
+    if (e) return hip_fail((hipError_t)e, "points_gather: kernel launch");
+    return CVGS_OK;
+}
+
+int cvgs_points_gather_host(const cvgs_point_gather_desc* desc, float* points_out, float* conf_out, int32_t* source_out) {
+    if (!desc) return fail(CVGS_ERR_INVALID, "points_gather_host: null argument");
+    GatherFrame f;
+    const int rc = check_gather_desc(*desc, points_out, conf_out, source_out, f);
+    if (rc) return rc;
+    const int live = gather_live(f.kept_count, f.max_out);
+    for (int j = 0; j < f.max_out; ++j) // k_points_gather's work-items, in order
+        for (int p = 0; p < f.n_points; ++p) {
+            switch (f.elem) {
+            case CVGS_HEAD_F32: gather_point<CVGS_HEAD_F32>(f, j, p, live); break;
+            case CVGS_HEAD_F16: gather_point<CVGS_HEAD_F16>(f, j, p, live); break;
+            default: gather_point<CVGS_HEAD_BF16>(f, j, p, live); break;
+            }
+        }
+    return CVGS_OK;
+}
+
 // ---- CircularTensor (the handle and the update routes: in front of this block) ---------------------------------
 int cvgs_circular_create(cvgs_circular_t* out, int32_t width, int32_t height, int32_t elem_type,
                          int32_t color_planes, int32_t batch, int32_t order, int32_t cp_mode, int32_t device_id) {

@@ -441,6 +441,29 @@ inline size_t head_scratch_bytes(int n) { return (size_t)kHeadMaxTiles * 4 + (si
 // validated by the caller; frames[0..n), n <= CVGS_HEAD_MAX_FRAMES.  Enqueues the score launch, then the compact launch.  0 or a HIP error code
 int launch_head(const HeadFrame* frames, int n, void* stream);
 
+// ---- landmarks of kept detections -> the points of cvgs_warp_tables_from_points (k_gather.hip): one frame's part of a cvgs_points_gather
+// call, 112 bytes
+struct GatherFrame {
+    const void* head;          // attribute a of candidate c: element c * cand_stride + a * attr_stride
+    const int32_t* kept_index; // int32[max_out]: select's index_out
+    const int32_t* kept_count; // live rows, or nullptr = max_out
+    const int32_t* cand_index; // int32[max_cand]: decode's index_out, or nullptr (kept_index holds raw candidate indices)
+    float* points_out;         // out: float[max_out][n_points][2]
+    float* conf_out;           // out: float[max_out][n_points], or nullptr
+    int32_t* source_out;       // out: int32[max_out], or nullptr
+    int32_t elem, max_cand;    // cvgs_head_elem; candidates
+    int32_t cand_stride, attr_stride;
+    int32_t point_attr, point_step;
+    int32_t n_points, conf_offset;
+    int32_t max_out, pad;
+    float xf[4];
+};
+static_assert(sizeof(GatherFrame) == 112, "GatherFrame layout");
+static_assert(sizeof(GatherFrame) * CVGS_GATHER_MAX_FRAMES <= 4096, "the descriptors of one call fit a 4 KB argument block");
+static constexpr int kGatherTile = 256;
+// validated by the caller; frames[0..n), n <= CVGS_GATHER_MAX_FRAMES.  0 or a HIP error code
+int launch_gather(const GatherFrame* frames, int n, void* stream);
+
 // ---- device-side arrival flags of the P2P fused-write exchange (k_exchange.hip) ----------------------------------------------
 #define CVGS_MAX_EXCHANGE_PEERS 16
 int launch_exchange_signal(void* const* peer_flags, int n, uint64_t value, uint64_t* counter, void* stream);

@@ -226,4 +226,56 @@ CVGS_HD inline bool head_member(float score, float thr, float c0, float c1, floa
     return score >= thr && !(c0 != c0 || c1 != c1 || c2 != c2 || c3 != c3);
 }
 
+// ---- landmarks of kept detections -> the points of cvgs_warp_tables_from_points (cvgs_hip_ext.h: cvgs_points_gather, THE CONTRACT) ----------
+// The element of attribute `attr` of candidate `c`, in size_t: 65534 * (2^31 - 1) + 8191 * (2^31 - 1) needs 48 bits.
+CVGS_HD inline size_t gather_elem_index(int32_t c, int32_t cand_stride, int32_t attr, int32_t attr_stride) {
+    return (size_t)c * (size_t)cand_stride + (size_t)attr * (size_t)attr_stride;
+}
+// Step 1.
+CVGS_HD inline int gather_live(const int32_t* kept_count, int max_out) {
+    const int live = kept_count ? *kept_count : max_out;
+    return live < 0 ? 0 : (live > max_out ? max_out : live);
+}
+// Step 2: the raw candidate of row j, or -1 for an invalid row.  An index is read only for j < live and only through an index that passed
+// its own test.
+CVGS_HD inline int32_t gather_source(const GatherFrame& f, int j, int live) {
+    if (j >= live) return -1;
+    const int32_t k = f.kept_index[j];
+    if (k < 0 || k >= f.max_cand) return -1;
+    if (!f.cand_index) return k;
+    const int32_t c = f.cand_index[k];
+    return c < 0 || c >= f.max_cand ? -1 : c;
+}
+template <int E>
+CVGS_HD inline float gather_read(const void* head, size_t idx) {
+    if (E == CVGS_HEAD_F32) return ((const float*)head)[idx];
+    const uint16_t h = ((const uint16_t*)head)[idx];
+    return E == CVGS_HEAD_F16 ? head_widen_f16(h) : head_widen_bf16(h);
+}
+// Step 3: detector -> frame pixels, two roundings; every NaN becomes the one quiet NaN.
+static constexpr uint32_t kGatherNaN = 0x7fc00000u;
+CVGS_HD inline float gather_map(float v, float s, float o) {
+    v = v * s;
+    v = v + o;
+    return v != v ? head_bits_f32(kGatherNaN) : v;
+}
+// Steps 2-5 for point p of row j: what work-item j * n_points + p of k_points_gather does and what the host entry loops over.  `f`'s output
+// pointers are the buffers written (the host entry puts its own there).
+template <int E>
+CVGS_HD inline void gather_point(const GatherFrame& f, int j, int p, int live) {
+    const int32_t c = gather_source(f, j, live);
+    float x = head_bits_f32(kGatherNaN), y = x, conf = 0.0f;
+    if (c >= 0) {
+        const int32_t a = f.point_attr + p * f.point_step;
+        x = gather_map(gather_read<E>(f.head, gather_elem_index(c, f.cand_stride, a, f.attr_stride)), f.xf[0], f.xf[2]);
+        y = gather_map(gather_read<E>(f.head, gather_elem_index(c, f.cand_stride, a + 1, f.attr_stride)), f.xf[1], f.xf[3]);
+        if (f.conf_out) conf = gather_read<E>(f.head, gather_elem_index(c, f.cand_stride, a + f.conf_offset, f.attr_stride));
+    }
+    const size_t o = (size_t)j * (size_t)f.n_points + (size_t)p;
+    f.points_out[2 * o] = x;
+    f.points_out[2 * o + 1] = y;
+    if (f.conf_out) f.conf_out[o] = conf;
+    if (p == 0 && f.source_out) f.source_out[j] = c;
+}
+
 } // namespace cvgs

@@ -923,6 +923,62 @@ def head_decode_host(desc, head):
     return bo, so, ko, io, int(co.value)
 
 
+# ---- the landmarks of kept detections -> warp_table_desc's points (include/cvgs_hip_ext.h: cvgs_points_gather) -------------------
+def point_gather_desc(head, elem_type, max_candidates, cand_stride, attr_stride, point_attr, point_step, n_points, max_out, kept_index, points_out,
+                      kept_count=None, cand_index=None, xform=(1.0, 1.0, 0.0, 0.0), conf_offset=-1, conf_out=None, source_out=None):
+    """One cvgs_point_gather_desc: the head is addressed as in head_desc; point p has x at attribute point_attr + p * point_step, y at the
+    next one and, with conf_offset >= 2, a confidence at point_attr + p * point_step + conf_offset.  kept_index / kept_count are select's
+    index_out / count_out, cand_index decode's index_out (None: kept_index holds raw candidate indices); xform = (sx, sy, ox, oy) maps
+    detector coordinates to frame pixels (letterbox_xform for edge coordinates; a detector that reports pixel-centre coordinates needs
+    ox + 0.5 * sx - 0.5 and oy + 0.5 * sy - 0.5).  points_out (float32 [max_out][n_points][2]) is what warp_table_desc takes as points,
+    with kept_count as its count.  All buffers are device buffers (torch tensors or raw pointers)."""
+    d = capi.PointGatherDesc()
+    d.struct_size = C.sizeof(capi.PointGatherDesc)
+    d.head = _dev_ptr(head) or None
+    d.elem_type, d.max_candidates = int(elem_type), int(max_candidates)
+    d.cand_stride, d.attr_stride = int(cand_stride), int(attr_stride)
+    d.point_attr, d.point_step, d.n_points, d.conf_offset = int(point_attr), int(point_step), int(n_points), int(conf_offset)
+    d.max_out = int(max_out)
+    d.kept_index, d.kept_count, d.cand_index = _dev_ptr(kept_index) or None, _dev_ptr(kept_count) or None, _dev_ptr(cand_index) or None
+    for i, v in enumerate(xform):
+        d.xform[i] = float(v)
+    d.points_out, d.conf_out, d.source_out = _dev_ptr(points_out) or None, _dev_ptr(conf_out) or None, _dev_ptr(source_out) or None
+    return d
+
+
+def points_gather(stream, descs):
+    """cvgs_points_gather: ONE small kernel on `stream` gathers the landmarks of every desc (point_gather_desc, at most 16); nothing is
+    copied to the host, nothing synchronises, and the call can be captured between boxes_select and warp_tables_from_points."""
+    lib = capi.load_library()
+    descs = list(descs)
+    arr = (capi.PointGatherDesc * len(descs))(*descs)
+    capi.check(lib.cvgs_points_gather(arr, len(descs), stream_handle(stream)))
+
+
+def points_gather_host(desc, head, kept_index, kept_count=None, cand_index=None):
+    """cvgs_points_gather_host: (points_out float32 [max_out, n_points, 2], conf_out float32 [max_out, n_points] or None without a
+    conf_offset, source_out int32 [max_out]) -- the bytes the kernel must write for `desc` -- computed on the CPU from HOST arrays: `head`
+    as head_decode_host takes it, `kept_index` / `cand_index` int32 numpy arrays, `kept_count` an int or None."""
+    import numpy as np
+    lib = capi.load_library()
+    d = capi.PointGatherDesc.from_buffer_copy(desc)
+    want = {HEAD_F32: (np.float32,), HEAD_F16: (np.float16, np.uint16), HEAD_BF16: (np.uint16,)}.get(int(d.elem_type), ())
+    if not isinstance(head, np.ndarray) or (want and head.dtype not in [np.dtype(t) for t in want]):
+        raise ValueError("head must be a numpy array of the descriptor's element type (bfloat16 as uint16 bits)")
+    for name, arr in (("kept_index", kept_index), ("cand_index", cand_index)):
+        if arr is not None and (not isinstance(arr, np.ndarray) or arr.dtype != np.int32 or not arr.flags.c_contiguous):
+            raise ValueError("%s must be a contiguous numpy array of int32" % name)
+    cnt = None if kept_count is None else C.c_int32(int(kept_count))
+    d.head, d.kept_index = head.ctypes.data, kept_index.ctypes.data
+    d.kept_count = None if cnt is None else C.addressof(cnt)
+    d.cand_index = None if cand_index is None else cand_index.ctypes.data
+    m, k = max(int(d.max_out), 1), max(int(d.n_points), 1)
+    po, so = np.empty((m, k, 2), np.float32), np.empty((m,), np.int32)
+    co = np.empty((m, k), np.float32) if int(d.conf_offset) != -1 else None
+    capi.check(lib.cvgs_points_gather_host(C.byref(d), po.ctypes.data, None if co is None else co.ctypes.data, so.ctypes.data))
+    return po, co, so
+
+
 # ---- device-built warp tables: aligned crops from a detector's device-side landmarks (include/cvgs_hip_ext.h) ----------------
 WARP_FIT_SIMILARITY, WARP_FIT_AFFINE3 = capi.WARP_FIT_SIMILARITY, capi.WARP_FIT_AFFINE3
 

@@ -861,6 +861,94 @@ inline auto resize(const DeviceCrops& crops, const cv::Scalar& backgroundValue_ 
     return rd;
 }
 
+// ---- the landmarks of kept detections -> the points DeviceWarps reads (engine extension: cvgs_points_gather, include/cvgs_hip_ext.h) ----
+// The link between DeviceBoxSelect and DeviceWarps: one small kernel on the stream follows the selector's indices (through the decoder's)
+// to the raw candidates, reads their landmarks from the head in place and maps them to frame pixels; nothing is copied to the host.
+//   cvGS::DevicePointGather gather(8400, 50, 5);                            // owns the points of up to 50 detections, 5 landmarks each
+//   gather.layout(d_head, CVGS_HEAD_BF16, 1, 8400, 5, 3).transform(sx, sy, ox, oy);   // a [4 + 1 + 5 * 3, 8400] head: x, y, conf from attribute 5
+//   gather.from(select, decode);                                            // select.indices() / count(), decode.indices()
+//   decode.enqueue(stream); select.enqueue(stream); gather.enqueue(stream);
+//   faces.update(stream, frame, gather.points(), gather.count(), CVGS_WARP_FIT_SIMILARITY, arcface5, cv::Size(112, 112));
+// The transform is the caller's: the selector's for a detector that reports edge coordinates; a detector that reports pixel-centre
+// coordinates needs ox + 0.5 * sx - 0.5 (oy + 0.5 * sy - 0.5), since the warp kernels take integer coordinates as pixel centres.
+// The second constructor takes caller-owned buffers and allocates nothing.
+class DevicePointGather {
+public:
+    DevicePointGather(int maxCandidates, int maxOut, int nPoints, bool withConf = false, bool withSource = false) {
+        init(maxCandidates, maxOut, nPoints);
+        if (maxCandidates < 1 || maxCandidates > 65535 || maxOut < 1 || maxOut > 65535 || nPoints < 1 || nPoints > CVGS_GATHER_MAX_POINTS)
+            throw std::runtime_error("cvGS::DevicePointGather: maxCandidates and maxOut in [1, 65535], nPoints in [1, 64]");
+        const size_t items = (size_t)maxOut * (size_t)nPoints;
+        d_.points_out = static_cast<float*>(own(items * 2 * sizeof(float)));
+        if (withConf) d_.conf_out = static_cast<float*>(own(items * sizeof(float)));
+        if (withSource) d_.source_out = static_cast<int32_t*>(own((size_t)maxOut * sizeof(int32_t)));
+    }
+    DevicePointGather(int maxCandidates, int maxOut, int nPoints, float* pointsOut, float* confOut = nullptr, int32_t* sourceOut = nullptr) {
+        init(maxCandidates, maxOut, nPoints);
+        d_.points_out = pointsOut; d_.conf_out = confOut; d_.source_out = sourceOut;
+    }
+    // where the head is (device pointer) and where its landmarks are: attribute a of candidate i at element i * candStride + a * attrStride,
+    // x of point p at attribute pointAttr + p * pointStep, y at the next one, its confidence at + confOffset (-1: none; given exactly when
+    // the object holds a confidence buffer)
+    DevicePointGather& layout(const void* head, cvgs_head_elem elemType, int candStride, int attrStride, int pointAttr, int pointStep, int confOffset = -1) {
+        d_.head = head; d_.elem_type = (int32_t)elemType; d_.cand_stride = candStride; d_.attr_stride = attrStride;
+        d_.point_attr = pointAttr; d_.point_step = pointStep; d_.conf_offset = confOffset;
+        return *this;
+    }
+    DevicePointGather& transform(float sx, float sy, float ox, float oy) { d_.xform[0] = sx; d_.xform[1] = sy; d_.xform[2] = ox; d_.xform[3] = oy; return *this; }
+    // the selector ran over the head's own candidates: its indices are raw candidate indices
+    DevicePointGather& from(const DeviceBoxSelect& select) {
+        if (select.maxOut() != d_.max_out) throw std::runtime_error("cvGS::DevicePointGather::from: the selector's maxOut differs");
+        if (select.desc().max_candidates != d_.max_candidates) throw std::runtime_error("cvGS::DevicePointGather::from: the selector's maxCandidates differs");
+        if (!select.indices()) throw std::runtime_error("cvGS::DevicePointGather::from: the selector was built without indices");
+        d_.kept_index = select.indices(); d_.kept_count = select.count(); d_.cand_index = nullptr;
+        return *this;
+    }
+    // the selector ran over the decoder's compacted list: its indices map to raw candidates through the decoder's
+    DevicePointGather& from(const DeviceBoxSelect& select, const DeviceHeadDecode& decode) {
+        if (decode.maxCandidates() != d_.max_candidates) throw std::runtime_error("cvGS::DevicePointGather::from: the decoder's maxCandidates differs");
+        if (!decode.indices()) throw std::runtime_error("cvGS::DevicePointGather::from: the decoder was built without indices");
+        from(select);
+        d_.cand_index = decode.indices();
+        return *this;
+    }
+    void enqueue(const cv::cuda::Stream& stream) const { fk::detail::check_status(cvgs_points_gather(&d_, 1, cv::cuda::StreamAccessor::getStream(stream))); }
+    // several frames (the cameras of a tick, at most 16) in ONE launch
+    static void enqueue(const cv::cuda::Stream& stream, const std::vector<const DevicePointGather*>& jobs) {
+        std::vector<cvgs_point_gather_desc> d;
+        d.reserve(jobs.size());
+        for (const DevicePointGather* j : jobs) {
+            if (!j) throw std::runtime_error("cvGS::DevicePointGather::enqueue: null DevicePointGather");
+            d.push_back(j->d_);
+        }
+        fk::detail::check_status(cvgs_points_gather(d.data(), (int32_t)d.size(), cv::cuda::StreamAccessor::getStream(stream)));
+    }
+    // what DeviceWarps::update accepts: maxOut x nPoints x 2 floats in frame pixels and the selector's count
+    const float* points() const { return d_.points_out; }
+    const int32_t* count() const { return d_.kept_count; }
+    const float* conf() const { return d_.conf_out; }       // nullptr when built without
+    const int32_t* source() const { return d_.source_out; } // nullptr when built without
+    int maxOut() const { return d_.max_out; }
+    int nPoints() const { return d_.n_points; }
+    const cvgs_point_gather_desc& desc() const { return d_; }
+private:
+    void init(int maxCandidates, int maxOut, int nPoints) {
+        std::memset(&d_, 0, sizeof(d_));
+        d_.struct_size = sizeof(d_);
+        d_.max_candidates = maxCandidates; d_.max_out = maxOut; d_.n_points = nPoints;
+        d_.elem_type = CVGS_HEAD_F32; d_.cand_stride = 1; d_.attr_stride = 1; d_.point_attr = 5; d_.point_step = 2; d_.conf_offset = -1;
+        d_.xform[0] = 1.f; d_.xform[1] = 1.f;
+    }
+    void* own(size_t bytes) {
+        void* p = nullptr;
+        fk::hip_check(hipMalloc(&p, bytes), "hipMalloc(point gather)");
+        owned_.push_back(std::shared_ptr<void>(p, [](void* q) { (void)hipFree(q); }));
+        return p;
+    }
+    cvgs_point_gather_desc d_;
+    std::vector<std::shared_ptr<void>> owned_;
+};
+
 // ---- aligned crops from a detector's device-side landmarks (engine extension: cvgs_warp_tables_from_points, include/cvgs_hip_ext.h) ----
 // Face alignment / oriented-box rectification without the host in the loop: the landmarks a network has just written on this GPU are
 // fitted to a template in ONE small kernel on the stream, and warp<WT, T>(deviceWarps) reads the resulting device warp table like any

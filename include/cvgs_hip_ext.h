@@ -3,8 +3,8 @@
  * descriptor queue (cvgs_queue_*: an opt-in submission path, frozen since round 5), the device-side arrival flags of the sharded
  * batched-crop path (cvgs_exchange_*: BASELINE cfg #5, SURVEY.md 8e option 2) and plane tables built on the device from a detector's
  * device-side boxes (cvgs_plane_tables_from_boxes) and warp tables fitted on the device to its device-side landmarks
- * (cvgs_warp_tables_from_points), device-side box selection (cvgs_boxes_select) and the decoding of a network's raw head into its
- * candidates (cvgs_head_decode).  The drop-in boundary -- what replaces
+ * (cvgs_warp_tables_from_points), device-side box selection (cvgs_boxes_select), the decoding of a network's raw head into its
+ * candidates (cvgs_head_decode) and the gather of the kept candidates' landmarks (cvgs_points_gather).  The drop-in boundary -- what replaces
  * fk::executeOperations and fk::CircularTensor (reference include/cvGPUSpeedup.cuh:464-627) -- is include/cvgs_hip.h alone; nothing
  * there depends on this file.  Same conventions: plain C, asynchronous on the given stream, 0 or a negative cvgs_status.
  */
@@ -381,9 +381,10 @@ int cvgs_boxes_select_host(const cvgs_box_select_desc* desc, void* boxes_out, in
  * every step is a comparison or a move.  Because order is preserved, select's tie rule ("lower index first") means the same on the
  * compacted list as on the dense one: cvgs_boxes_select over the decoder's outputs, with the same score_threshold, returns exactly what
  * it returns over the dense per-candidate (score, class) arrays -- only its index_out differs, and it maps back to candidate indices
- * through the decoder's index_out (which is what a caller gathers landmarks or masks of kept candidates with).
+ * through the decoder's index_out (which is what cvgs_points_gather, below, follows to the landmarks of kept candidates, and what a
+ * caller gathers their masks with).
  * OUT OF SCOPE.  Heads are expected to hold probabilities (exported graphs apply the sigmoid themselves): there is no sigmoid / exp, no
- * anchor or DFL decoding, no device `count` INPUT, and no gather of landmarks of kept candidates.
+ * anchor or DFL decoding and no device `count` INPUT.
  * HOW (csrc/k_head.hip): both launches have the grid (256 candidates per workgroup, frame).  The score launch computes steps 1-4 for every
  * candidate and stores its score, class and member flag, and the tile's member count (ballot + popcount, the four wave totals through LDS),
  * in `scratch`.  It has two forms, chosen on the host by stride: attr_stride != 1 (and any stride pair): one lane per candidate walking the
@@ -425,6 +426,78 @@ typedef struct cvgs_head_desc {
 size_t cvgs_head_decode_scratch_bytes(int32_t max_candidates);
 int cvgs_head_decode(const cvgs_head_desc* descs, int32_t n, cvgs_stream_t stream); /* n = 1..CVGS_HEAD_MAX_FRAMES frames, one call */
 int cvgs_head_decode_host(const cvgs_head_desc* desc, float* boxes_out, float* scores_out, int32_t* classes_out, int32_t* index_out, int32_t* count_out);
+
+/* ---- the landmarks of kept detections -> the points cvgs_warp_tables_from_points reads ----------------------------------------------------
+ * The link between the box path and the aligned-crop path.  Face and pose detectors emit the landmarks as further attributes of each
+ * candidate of the same raw head -- YOLOv8-pose / YOLO-face: [4 + 1 + K * 3, N] (x, y, confidence per point); SCRFD / RetinaFace exports:
+ * [N, 4 + 1 + 2 K] -- and after cvgs_head_decode and cvgs_boxes_select the survivors are known only as two device index lists: select's
+ * index_out into the compacted list, decode's index_out from there into the head.  cvgs_points_gather enqueues ONE small kernel on
+ * `stream` (csrc/k_gather.hip) for up to 16 frames and nothing else: no allocation, no staging, no copy, no synchronisation, so the call
+ * can be captured between cvgs_boxes_select and cvgs_warp_tables_from_points.  It reads the head in place (fp32 / fp16 / bf16, the two
+ * strides of cvgs_head_desc), follows the indices to the raw candidates, maps every landmark to frame pixels with select's xform rule and
+ * writes points_out: by construction a valid `points` of a cvgs_warp_table_desc with max_items = max_out and the same n_points, whose
+ * `count` is select's own count_out.  Its cost: see README.md.
+ *
+ * Attribute a of candidate c is element head[c * cand_stride + a * attr_stride] (in size_t, in elements of elem_type), as for
+ * cvgs_head_decode.  Point p has x at attribute point_attr + p * point_step, y at the next one and (conf_offset >= 2) a confidence at
+ * point_attr + p * point_step + conf_offset.
+ *
+ * THE CONTRACT.  One text for the kernel and for cvgs_points_gather_host (csrc/cvgs_geometry.h: gather_live, gather_source,
+ * gather_elem_index, gather_map, gather_point), compiled with -ffp-contract=off, so the device writes the host entry's bytes.  Per frame,
+ * for every row j < max_out:
+ *   1. live = clamp(kept_count ? *kept_count : max_out, 0, max_out).
+ *   2. Row j is VALID iff j < live, k = kept_index[j] lies in [0, max_candidates) and -- with cand_index -- c = cand_index[k] lies in
+ *      [0, max_candidates); without cand_index c = k.  cvgs_head_decode writes -1 behind its count, so a stale k fails here.  Nothing is
+ *      dereferenced with an index that failed its test, and indices are read only for j < live: the call is SAFE WHATEVER THE DEVICE
+ *      BUFFERS HOLD, like the table builders.
+ *   3. A valid row, point p: x and y are widened to fp32 exactly (as cvgs_head_decode's step 1), then x = x * sx; x = x + ox (two
+ *      roundings, no fma) and the same for y with sy, oy -- select's step 4.  A result that is NaN is stored as the ONE bit pattern
+ *      0x7fc00000, so host and device cannot differ in a payload; +-inf is stored as it comes.  conf_out[j][p] = the widened confidence
+ *      attribute as read; source_out[j] = c.
+ *   4. An invalid row: every coordinate is 0x7fc00000, every confidence 0.0f, source_out[j] = -1.  NaN and not 0: three coincident zero
+ *      points are a legal input of the AFFINE3 fit, whereas a non-finite coordinate is what cvgs_warp_tables_from_points rejects under
+ *      both fits -- even for a caller who forgets to pass the count.
+ *   5. EVERY output element is written on every call.
+ * The coordinates are NOT clamped: a landmark outside the frame is a legitimate input of a fit.
+ * THE XFORM is the caller's, (sx, sy, ox, oy) as in cvgs_box_select_desc: frame = detector * s + o.  For a detector whose coordinates are
+ * EDGE coordinates of its letterboxed input (pixel i spans [i, i + 1), as boxes are) it is select's own.  The warp kernels take integer
+ * coordinates as PIXEL CENTRES (cv::warpAffine's convention), as do landmark heads trained on such coordinates: a detector that reports
+ * pixel-centre coordinates in its input needs ox + 0.5 * sx - 0.5 (and oy + 0.5 * sy - 0.5) in place of ox (oy).
+ * HOW (csrc/k_gather.hip): grid (ceil(max over frames of max_out * n_points / 256), frame), 256 work-items; work-item t of a frame owns
+ * (j, p) = (t / n_points, t % n_points), so consecutive lanes store consecutive (x, y) pairs and a wave's store is one contiguous span;
+ * the lane with p == 0 stores source_out[j].  The descriptors travel in the kernel arguments.  No LDS, no atomic.  The work is a few
+ * thousand elements: the launch boundary is the cost.
+ * Validation happens completely on the host before the first HIP call (a machine without a GPU can test it): null descriptors, null
+ * head / kept_index / points_out, struct_size, flags, reserved, n outside 1..16, a bad elem_type, max_candidates or max_out outside
+ * 1..65535, cand_stride or attr_stride < 1, point_step < 2, n_points outside 1..64, a conf_offset other than -1 or outside
+ * [2, point_step), conf_out without conf_offset or conf_offset without conf_out, an addressed attribute outside 0..8191 (point_attr;
+ * point_attr + (n_points - 1) * point_step + max(1, conf_offset)), misaligned pointers (head: its element size; everything else: 4
+ * bytes), sx or sy not finite or <= 0, ox or oy not finite, output buffers of one call that overlap -> CVGS_ERR_INVALID.
+ *   cvgs_points_gather_host  the same descriptor with HOST head / kept_index / kept_count / cand_index; desc's output pointers are ignored
+ *                            and the results go to points_out (float[max_out][n_points][2]), conf_out (given exactly when conf_offset
+ *                            is) and source_out (optional).  Runs the shared text on the CPU and writes the bytes the kernel must write;
+ *                            makes no HIP call.
+ * No reference counterpart.                                                                                                          */
+#define CVGS_GATHER_MAX_FRAMES 16
+#define CVGS_GATHER_MAX_POINTS 64
+typedef struct cvgs_point_gather_desc {
+    uint32_t struct_size, flags;          /* sizeof(cvgs_point_gather_desc); flags: must be 0 */
+    const void* head;                     /* device: attribute a of candidate i at element i * cand_stride + a * attr_stride */
+    int32_t elem_type, max_candidates;    /* cvgs_head_elem; 1..65535 */
+    int32_t cand_stride, attr_stride;     /* in elements: >= 1 */
+    int32_t point_attr, point_step;       /* x of point p = attribute point_attr + p * point_step, y = that + 1; point_step >= 2 */
+    int32_t n_points, conf_offset;        /* 1..CVGS_GATHER_MAX_POINTS; the confidence of point p = attribute point_attr + p * point_step + conf_offset, or -1: none */
+    int32_t max_out, reserved;            /* 1..65535; 0 */
+    const int32_t* kept_index;            /* device int32[max_out]: select's index_out */
+    const int32_t* kept_count;            /* device int32, or NULL = max_out: select's count_out */
+    const int32_t* cand_index;            /* device int32[max_candidates], or NULL: decode's index_out (kept_index then indexes the compacted list) */
+    float xform[4];                       /* (sx, sy, ox, oy): frame = detector * s + o */
+    float* points_out;                    /* device float[max_out][n_points][2] */
+    float* conf_out;                      /* device float[max_out][n_points], or NULL (required NULL when conf_offset == -1) */
+    int32_t* source_out;                  /* device int32[max_out], or NULL: the raw candidate index of each row, -1 for an invalid row */
+} cvgs_point_gather_desc;
+int cvgs_points_gather(const cvgs_point_gather_desc* descs, int32_t n, cvgs_stream_t stream); /* n = 1..CVGS_GATHER_MAX_FRAMES frames, one call */
+int cvgs_points_gather_host(const cvgs_point_gather_desc* desc, float* points_out, float* conf_out, int32_t* source_out);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,4 @@
-// cvgs_device.h -- structs shared by the host-side lowering (cvgs_api.cpp) and the HIP kernels.
+// cvgs_device.h -- structs shared by the host files (cvgs_api.cpp: lowering; cvgs_detect.cpp: detector stages) and the HIP kernels.
 // Everything here crosses the host->device boundary BY VALUE inside the kernel-argument block,
 // exactly like the reference passes its IOp parameters, so one fused chain is one
 // launch with no side uploads.  Large crop lists use a device-resident plane table instead.

@@ -1,5 +1,5 @@
 // cvgs_geometry.h -- the per-plane resize geometry, the box -> rectangle rule and the landmark -> warp fit, ONE spelling for the host side
-// (cvgs_api.cpp) and the device-side table builders (k_boxes.hip, k_points.hip).  Bit-exactness of fx / fy is part of the parity contract: both sides compile this text
+// (cvgs_api.cpp: lowering; cvgs_detect.cpp: the table builders' and detector stages' host entries) and the device-side table builders (k_boxes.hip, k_points.hip).  Bit-exactness of fx / fy is part of the parity contract: both sides compile this text
 // with -ffp-contract=off, gfx950 divides fp32 and fp64 correctly rounded (HIP's default), and roundf is exact on both -- so a table
 // written on the device equals the host-built one byte for byte (tests/test_gpu_boxes.py compares them).
 #pragma once

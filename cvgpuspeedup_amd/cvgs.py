@@ -748,6 +748,21 @@ def _dev_ptr(x):
     return int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
 
 
+def _submit_descs(entry, desc_type, stream, descs):
+    """One call of a detector-side entry point (csrc/cvgs_detect.cpp): the descriptors as one C array, their number, the stream."""
+    descs = list(descs)
+    arr = (desc_type * len(descs))(*descs)
+    capi.check(getattr(capi.load_library(), entry)(arr, len(descs), stream_handle(stream)))
+
+
+def _check_head_array(d, head):
+    """The host entries read a raw head from a numpy array of the descriptor's element type (an unknown type is the library's to refuse)."""
+    import numpy as np
+    want = {HEAD_F32: (np.float32,), HEAD_F16: (np.float16, np.uint16), HEAD_BF16: (np.uint16,)}.get(int(d.elem_type), ())
+    if not isinstance(head, np.ndarray) or (want and head.dtype not in [np.dtype(t) for t in want]):
+        raise ValueError("head must be a numpy array of the descriptor's element type (bfloat16 as uint16 bits)")
+
+
 def box_table_desc(frame, boxes, table, max_boxes, dsize, ar=IGNORE_AR, box_format=BOX_XYXY_F32, count=None, rects=None,
                    kind=capi.READ_RESIZE_LINEAR, layout=capi.YUV_NV12):
     """One cvgs_box_table_desc: `frame` is the GpuMat of the WHOLE frame (an NV12 / NV21 luma view for kind READ_NV12_RESIZE_LINEAR);
@@ -766,10 +781,7 @@ def box_table_desc(frame, boxes, table, max_boxes, dsize, ar=IGNORE_AR, box_form
 def plane_tables_from_boxes(stream, descs):
     """cvgs_plane_tables_from_boxes: ONE small kernel on `stream` writes the device plane tables of every desc (box_table_desc) from the
     boxes in device memory; nothing is copied to the host, nothing synchronises, and the launch can be captured."""
-    lib = capi.load_library()
-    descs = list(descs)
-    arr = (capi.BoxTableDesc * len(descs))(*descs)
-    capi.check(lib.cvgs_plane_tables_from_boxes(arr, len(descs), stream_handle(stream)))
+    _submit_descs("cvgs_plane_tables_from_boxes", capi.BoxTableDesc, stream, descs)
 
 
 def resize_boxes(frame, table, max_boxes, dsize, background=None, ar=IGNORE_AR, yuv=None, layout=capi.YUV_NV12, interp=INTER_LINEAR):
@@ -826,10 +838,7 @@ def box_select_desc(frame_size, boxes, scores, max_candidates, scratch, boxes_ou
 def boxes_select(stream, descs):
     """cvgs_boxes_select: two small kernels on `stream` (rank, suppress) select the boxes of every desc (box_select_desc, at most 16);
     nothing is copied to the host, nothing synchronises, and the call can be captured in front of plane_tables_from_boxes."""
-    lib = capi.load_library()
-    descs = list(descs)
-    arr = (capi.BoxSelectDesc * len(descs))(*descs)
-    capi.check(lib.cvgs_boxes_select(arr, len(descs), stream_handle(stream)))
+    _submit_descs("cvgs_boxes_select", capi.BoxSelectDesc, stream, descs)
 
 
 def boxes_select_host(desc, boxes, scores, classes=None, count=None):
@@ -898,10 +907,7 @@ def head_desc(head, elem_type, max_candidates, cand_stride, attr_stride, num_cla
 def head_decode(stream, descs):
     """cvgs_head_decode: two small kernels on `stream` (score, compact) decode the head of every desc (head_desc, at most 16); nothing
     is copied to the host, nothing synchronises, and the call can be captured in front of boxes_select."""
-    lib = capi.load_library()
-    descs = list(descs)
-    arr = (capi.HeadDesc * len(descs))(*descs)
-    capi.check(lib.cvgs_head_decode(arr, len(descs), stream_handle(stream)))
+    _submit_descs("cvgs_head_decode", capi.HeadDesc, stream, descs)
 
 
 def head_decode_host(desc, head):
@@ -911,9 +917,7 @@ def head_decode_host(desc, head):
     import numpy as np
     lib = capi.load_library()
     d = capi.HeadDesc.from_buffer_copy(desc)
-    want = {HEAD_F32: (np.float32,), HEAD_F16: (np.float16, np.uint16), HEAD_BF16: (np.uint16,)}.get(int(d.elem_type), ())
-    if not isinstance(head, np.ndarray) or (want and head.dtype not in [np.dtype(t) for t in want]):
-        raise ValueError("head must be a numpy array of the descriptor's element type (bfloat16 as uint16 bits)")
+    _check_head_array(d, head)
     d.head = head.ctypes.data
     n = max(int(d.max_candidates), 1)
     bo, so = np.empty((n, 4), np.float32), np.empty((n,), np.float32)
@@ -949,10 +953,7 @@ def point_gather_desc(head, elem_type, max_candidates, cand_stride, attr_stride,
 def points_gather(stream, descs):
     """cvgs_points_gather: ONE small kernel on `stream` gathers the landmarks of every desc (point_gather_desc, at most 16); nothing is
     copied to the host, nothing synchronises, and the call can be captured between boxes_select and warp_tables_from_points."""
-    lib = capi.load_library()
-    descs = list(descs)
-    arr = (capi.PointGatherDesc * len(descs))(*descs)
-    capi.check(lib.cvgs_points_gather(arr, len(descs), stream_handle(stream)))
+    _submit_descs("cvgs_points_gather", capi.PointGatherDesc, stream, descs)
 
 
 def points_gather_host(desc, head, kept_index, kept_count=None, cand_index=None):
@@ -962,9 +963,7 @@ def points_gather_host(desc, head, kept_index, kept_count=None, cand_index=None)
     import numpy as np
     lib = capi.load_library()
     d = capi.PointGatherDesc.from_buffer_copy(desc)
-    want = {HEAD_F32: (np.float32,), HEAD_F16: (np.float16, np.uint16), HEAD_BF16: (np.uint16,)}.get(int(d.elem_type), ())
-    if not isinstance(head, np.ndarray) or (want and head.dtype not in [np.dtype(t) for t in want]):
-        raise ValueError("head must be a numpy array of the descriptor's element type (bfloat16 as uint16 bits)")
+    _check_head_array(d, head)
     for name, arr in (("kept_index", kept_index), ("cand_index", cand_index)):
         if arr is not None and (not isinstance(arr, np.ndarray) or arr.dtype != np.int32 or not arr.flags.c_contiguous):
             raise ValueError("%s must be a contiguous numpy array of int32" % name)
@@ -1007,10 +1006,7 @@ def warp_table_desc(frame, points, table, max_items, dsize, tmpl, fit=WARP_FIT_S
 def warp_tables_from_points(stream, descs):
     """cvgs_warp_tables_from_points: ONE small kernel on `stream` fits the transforms of every desc (warp_table_desc) to the landmarks in
     device memory and writes the device warp tables; nothing is copied to the host, nothing synchronises, and the launch can be captured."""
-    lib = capi.load_library()
-    descs = list(descs)
-    arr = (capi.WarpTableDesc * len(descs))(*descs)
-    capi.check(lib.cvgs_warp_tables_from_points(arr, len(descs), stream_handle(stream)))
+    _submit_descs("cvgs_warp_tables_from_points", capi.WarpTableDesc, stream, descs)
 
 
 def build_warp_table_host(desc, points, count=None):

@@ -409,8 +409,8 @@ def _cast(x, dst, truncating, sw):
         return Val(x.v, x.b, dst)  # 8- and 16-bit integers and 16-bit floats widen exactly
     if dst == DEPTH_64F:
         if src == DEPTH_32F:
-            return Val(x.v, x.b, dst)  # every fp32 value is a double: exact, no bound added (64F ARITHMETIC stays outside the model)
-        raise NotImplementedError("CV_64F chains are outside the model")
+            return Val(x.v, x.b, dst)  # every fp32 value is a double: exact, no bound added (64F ARITHMETIC: tests/exact_model.py)
+        raise NotImplementedError("CV_64F chains are held by the exact model: tests/exact_model.py")
     lo, hi = INT_RANGE[dst]
     if src in INT_RANGE:
         a, c = np.clip(x.v - x.b, lo, hi), np.clip(x.v + x.b, lo, hi)
@@ -447,7 +447,7 @@ def apply_op(x, opcode, aux, operand, sw=SPEC):
         out = Val(lum.v[..., None], lum.b[..., None], DEPTH_32F)
         return out if x.depth == DEPTH_32F else _cast(out, x.depth, False, SPEC)
     if x.depth != DEPTH_32F:
-        raise NotImplementedError("arithmetic on integer-typed values is outside the model")
+        raise NotImplementedError("arithmetic on integer-typed values is held by the exact model: tests/exact_model.py")
     c = f32(list(operand)[:x.v.shape[-1]])  # the scalar narrowed double -> float, part of the definition
     if opcode == OP_MUL:
         return x.mul(c)

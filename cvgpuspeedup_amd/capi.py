@@ -134,6 +134,17 @@ class WarpTableDesc(C.Structure):
                 ("count", C.c_void_p), ("table_out", C.c_void_p), ("valid_out", C.c_void_p)]
 
 
+# device-built warp tables from boxes (include/cvgs_hip_ext.h: cvgs_warp_tables_from_boxes)
+BOX_SHAPE_STRETCH, BOX_SHAPE_EXPAND = 0, 1
+
+
+class BoxWarpDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("frame", Image2D), ("src_type", C.c_int32), ("read_kind", C.c_int32),
+                ("dst_width", C.c_int32), ("dst_height", C.c_int32), ("shape", C.c_int32), ("max_items", C.c_int32),
+                ("scale", C.c_float * 2), ("pad", C.c_float * 2), ("boxes", C.c_void_p), ("count", C.c_void_p), ("table_out", C.c_void_p),
+                ("boxes_out", C.c_void_p), ("valid_out", C.c_void_p)]
+
+
 # device-side box selection (include/cvgs_hip_ext.h: cvgs_boxes_select)
 CAND_XYXY_F32, CAND_CXCYWH_F32 = 0, 1
 SELECT_MAX_FRAMES, SELECT_MAX_PRE_NMS = 16, 1024
@@ -214,6 +225,8 @@ SYMBOLS = [
     ("cvgs_warp_table_bytes", C.c_size_t, [C.c_int32]),
     ("cvgs_warp_tables_from_points", C.c_int, [C.POINTER(WarpTableDesc), C.c_int32, C.c_void_p]),
     ("cvgs_warp_table_build_host", C.c_int, [C.POINTER(WarpTableDesc), C.c_void_p]),
+    ("cvgs_warp_tables_from_boxes", C.c_int, [C.POINTER(BoxWarpDesc), C.c_int32, C.c_void_p]),
+    ("cvgs_warp_table_from_boxes_host", C.c_int, [C.POINTER(BoxWarpDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cvgs_boxes_select_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32]),
     ("cvgs_boxes_select", C.c_int, [C.POINTER(BoxSelectDesc), C.c_int32, C.c_void_p]),
     ("cvgs_boxes_select_host", C.c_int, [C.POINTER(BoxSelectDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

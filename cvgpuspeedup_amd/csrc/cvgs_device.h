@@ -390,6 +390,25 @@ static_assert(sizeof(PointFrame) * CVGS_WARP_MAX_FRAMES <= 4096, "the descriptor
 // validated by the caller; frames[0..n), n <= CVGS_WARP_MAX_FRAMES.  0 or a HIP error code
 int launch_points(const PointFrame* frames, int n, void* stream);
 
+// ---- device-built warp tables from boxes (k_boxwarp.hip): one frame's part of a cvgs_warp_tables_from_boxes launch, 96 bytes ----
+struct BoxWarpFrame {
+    const uint8_t* data;     // the whole frame
+    const float* boxes;      // [max_items][4]: xa ya xb yb, edge coordinates
+    const int32_t* count;    // live items, or nullptr = max_items
+    WarpPlane* table;        // out: WarpPlane[max_items]
+    float* boxes_out;        // out: float[max_items][4], or nullptr
+    int32_t* valid;          // out: int32[max_items], or nullptr
+    int32_t w, h, step;
+    int32_t dst_w, dst_h;
+    int32_t shape, max_items; // cvgs_box_shape
+    float scale[2], pad[2];
+    int32_t reserved;
+};
+static_assert(sizeof(BoxWarpFrame) == 96, "BoxWarpFrame layout");
+static_assert(sizeof(BoxWarpFrame) * CVGS_WARP_MAX_FRAMES <= 4096, "the descriptors of one launch fit a 4 KB argument block");
+// validated by the caller; frames[0..n), n <= CVGS_WARP_MAX_FRAMES.  0 or a HIP error code
+int launch_box_warps(const BoxWarpFrame* frames, int n, void* stream);
+
 // ---- device-side box selection (k_select.hip): one frame's part of a cvgs_boxes_select call, 136 bytes ----------------------------------
 struct SelectFrame {
     const float* boxes;      // candidate i: boxes[i * box_stride + 0..3]

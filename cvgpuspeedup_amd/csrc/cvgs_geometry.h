@@ -146,6 +146,43 @@ CVGS_HD inline bool warp_fit(int fit, int k, const float* pts, const float* tmpl
     return true;
 }
 
+// ---- a box -> the inverse warp of its context crop (cvgs_hip_ext.h: cvgs_warp_tables_from_boxes, THE CONTRACT) ---------------------------
+// Steps 1-7 for ONE item: `box` = (xa, ya, xb, yb), edge coordinates, read in place; `scale` / `pad` = the descriptor's two floats each.
+// m receives the nine floats of a WarpPlane::m, rect the four of boxes_out[i] (always written: zeros for an invalid item).  Returns
+// whether the item is valid.  Double throughout, one rounding per operation in the order written, narrowed at the end: host and device
+// compile this text with -ffp-contract=off and divide correctly rounded, so they agree bit for bit.
+// `live`: the item's index lies below the (clamped) count.  The caller has validated shape, scale, pad and the target on the host.
+CVGS_HD inline bool box_warp_fit(int shape, const float* box, const float* scale, const float* pad, int dst_w, int dst_h, bool live, float* m, float* rect) {
+    warp_fit_invalid(m);
+    rect[0] = 0.f; rect[1] = 0.f; rect[2] = 0.f; rect[3] = 0.f;
+    if (!live) return false;
+    const double xa = (double)box[0], ya = (double)box[1], xb = (double)box[2], yb = (double)box[3];
+    if (!(fit_finite(xa) && fit_finite(ya) && fit_finite(xb) && fit_finite(yb))) return false;
+    const double w = xb - xa, h = yb - ya;
+    if (!(w > 0.0 && h > 0.0)) return false;
+    const double cx = (xa + xb) * 0.5, cy = (ya + yb) * 0.5;
+    double w1 = w * (double)scale[0];
+    w1 = w1 + (double)pad[0];
+    double h1 = h * (double)scale[1];
+    h1 = h1 + (double)pad[1];
+    const double dw = (double)dst_w, dh = (double)dst_h;
+    if (shape == CVGS_BOX_SHAPE_EXPAND) { // the shorter side grows; no rounded ratio of the target's sides
+        const double t1 = w1 * dh, t2 = h1 * dw;
+        if (t1 > t2) h1 = t1 / dw;
+        else if (t2 > t1) w1 = t2 / dh;
+    }
+    const double hw = w1 * 0.5, hh = h1 * 0.5;
+    const double m0 = w1 / dw, m4 = h1 / dh;
+    const double m2 = (cx - hw) + (m0 * 0.5 - 0.5), m5 = (cy - hh) + (m4 * 0.5 - 0.5);
+    const float f0 = (float)m0, f2 = (float)m2, f4 = (float)m4, f5 = (float)m5;
+    if (!(fit_finite((double)f0) && fit_finite((double)f2) && fit_finite((double)f4) && fit_finite((double)f5))) return false;
+    m[0] = f0; m[2] = f2;
+    m[4] = f4; m[5] = f5;
+    rect[0] = (float)(cx - hw); rect[1] = (float)(cy - hh);
+    rect[2] = (float)(cx + hw); rect[3] = (float)(cy + hh);
+    return true;
+}
+
 // ---- detector candidates -> selected boxes (cvgs_hip_ext.h: cvgs_boxes_select, THE CONTRACT) ---------------------------------------------
 // Steps 2-5 for ONE live candidate: `c` = its four coordinates as read, `xf` = (sx, sy, ox, oy).  Returns whether it is a member; then
 // out[0..3] = (xa, ya, xb, yb) clamped into the frame.  Strict fp32, one rounding per operation in the order written (both sides compile

@@ -1,5 +1,5 @@
 // cvgs_host.h -- what the two host files of the C-ABI share: cvgs_api.cpp (chains: lowering, dispatch, ticks, CircularTensor, the queue) and
-// cvgs_detect.cpp (the detector-side stages and their table builders).  Host only: no kernel includes this, and it needs no HIP header.
+// cvgs_detect.cpp / cvgs_boxwarp.cpp (the detector-side stages and their table builders).  Host only: no kernel includes this, and it needs no HIP header.
 #pragma once
 
 #include <stdint.h>

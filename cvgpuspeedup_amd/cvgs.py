@@ -1028,8 +1028,58 @@ def build_warp_table_host(desc, points, count=None):
     return bytes(out), list(valid)
 
 
+# ---- device-built warp tables: context crops from a detector's device-side boxes (include/cvgs_hip_ext.h) --------------------
+BOX_SHAPE_STRETCH, BOX_SHAPE_EXPAND = capi.BOX_SHAPE_STRETCH, capi.BOX_SHAPE_EXPAND
+
+
+def box_warp_desc(frame, boxes, table, max_items, dsize, shape=BOX_SHAPE_EXPAND, scale=(1.25, 1.25), pad=(0.0, 0.0), warp_type=WARP_AFFINE,
+                  count=None, boxes_out=None, valid=None):
+    """One cvgs_box_warp_desc: `frame` is the GpuMat of the WHOLE frame; boxes (float32 [max_items][4], XYXY edge coordinates: select's
+    boxes_out) / count / table / boxes_out / valid are device buffers (torch tensors or raw pointers).  Each box is grown by `scale` and
+    `pad` per axis, its shorter side grown to dsize's aspect ratio (BOX_SHAPE_EXPAND) or not (BOX_SHAPE_STRETCH), and sampled to dsize
+    even where it leaves the frame (0 there)."""
+    d = capi.BoxWarpDesc()
+    d.struct_size = C.sizeof(capi.BoxWarpDesc)
+    d.frame = frame.image2d()
+    d.src_type = frame.cv_type
+    d.read_kind = capi.READ_WARP_AFFINE if warp_type == WARP_AFFINE else capi.READ_WARP_PERSPECTIVE
+    d.dst_width, d.dst_height = int(dsize[0]), int(dsize[1])
+    d.shape, d.max_items = int(shape), int(max_items)
+    d.scale[0], d.scale[1] = float(scale[0]), float(scale[1])
+    d.pad[0], d.pad[1] = float(pad[0]), float(pad[1])
+    d.boxes, d.count, d.table_out = _dev_ptr(boxes) or None, _dev_ptr(count) or None, _dev_ptr(table) or None
+    d.boxes_out, d.valid_out = _dev_ptr(boxes_out) or None, _dev_ptr(valid) or None
+    return d
+
+
+def warp_tables_from_boxes(stream, descs):
+    """cvgs_warp_tables_from_boxes: ONE small kernel on `stream` shapes the boxes of every desc (box_warp_desc, at most 16) and writes the
+    device warp tables; nothing is copied to the host, nothing synchronises, and the launch can be captured.  warp_table reads them."""
+    _submit_descs("cvgs_warp_tables_from_boxes", capi.BoxWarpDesc, stream, descs)
+
+
+def warp_table_from_boxes_host(desc, boxes, count=None):
+    """cvgs_warp_table_from_boxes_host: (table bytes, 64 per item; boxes_out float32 [max_items, 4]; valid int32 [max_items]) -- the bytes
+    the kernel must write for `desc` -- computed on the CPU from HOST `boxes` (anything numpy turns into float32 [max_items][4]) and
+    `count` (int or None)."""
+    import numpy as np
+    lib = capi.load_library()
+    d = capi.BoxWarpDesc.from_buffer_copy(desc)
+    bx = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1)
+    n = max(int(d.max_items), 1)
+    if bx.size != int(d.max_items) * 4:
+        raise ValueError("boxes must hold max_items x 4 floats")
+    cnt = None if count is None else C.c_int32(int(count))
+    out = (C.c_uint8 * (64 * n))()
+    bo, vo = np.empty((n, 4), np.float32), np.empty((n,), np.int32)
+    d.boxes = bx.ctypes.data
+    d.count = None if cnt is None else C.addressof(cnt)
+    capi.check(lib.cvgs_warp_table_from_boxes_host(C.byref(d), out, bo.ctypes.data, vo.ctypes.data))
+    return bytes(out), bo, vo
+
+
 def warp_table(warp_type, frame, table, max_items, dsize, used_planes=None, default_value=None):
-    """The batched read "warp over a device-built table of `frame`" (warp_tables_from_points): batch = max_items, planes at or beyond
+    """The batched read "warp over a device-built table of `frame`" (warp_tables_from_points / warp_tables_from_boxes): batch = max_items, planes at or beyond
     used_planes take default_value, validity is per plane inside the table.  The chain states the whole frame's byte range."""
     kind = capi.READ_WARP_AFFINE if warp_type == WARP_AFFINE else capi.READ_WARP_PERSPECTIVE
     rd = ReadIOp(kind, frame.cv_type, None, used_planes, (int(dsize[0]), int(dsize[1])), IGNORE_AR, default_value, table=_dev_ptr(table),

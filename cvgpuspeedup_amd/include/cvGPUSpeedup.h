@@ -991,6 +991,27 @@ public:
         fk::detail::check_status(cvgs_warp_tables_from_points(&d, 1, cv::cuda::StreamAccessor::getStream(stream)));
         frame_ = frame; dsize_ = dsize;
     }
+    // enqueue the box builder for ONE frame (cvgs_warp_tables_from_boxes): `boxes` = device float32 [maxItems][4] (xa, ya, xb, yb), edge
+    // coordinates in frame pixels (DeviceBoxSelect's boxes); `count` = device int32 or nullptr.  Each box grows by `scale` and `pad` per
+    // axis, its shorter side to dsize's aspect ratio (CVGS_BOX_SHAPE_EXPAND), and is sampled to dsize even where it leaves the frame (0
+    // there).  `boxesOut` (optional, device float32 [maxItems][4]) receives the shaped rectangles, unclamped.
+    void updateFromBoxes(const cv::cuda::Stream& stream, const cv::cuda::GpuMat& frame, const float* boxes, const int32_t* count, const cv::Size& dsize,
+                         cvgs_box_shape shape = CVGS_BOX_SHAPE_EXPAND, const cv::Point2f& scale = cv::Point2f(1.25f, 1.25f),
+                         const cv::Point2f& pad = cv::Point2f(0.f, 0.f), float* boxesOut = nullptr) {
+        cvgs_box_warp_desc d;
+        std::memset(&d, 0, sizeof(d));
+        d.struct_size = sizeof(d);
+        d.frame = cvgs_image2d{frame.data, frame.cols, frame.rows, (int32_t)frame.step, 0};
+        d.src_type = frame.type();
+        d.read_kind = CVGS_READ_WARP_AFFINE;
+        d.dst_width = dsize.width; d.dst_height = dsize.height;
+        d.shape = (int32_t)shape; d.max_items = max_;
+        d.scale[0] = scale.x; d.scale[1] = scale.y; d.pad[0] = pad.x; d.pad[1] = pad.y;
+        d.boxes = boxes; d.count = count;
+        d.table_out = table_.get(); d.boxes_out = boxesOut; d.valid_out = static_cast<int32_t*>(valid_.get());
+        fk::detail::check_status(cvgs_warp_tables_from_boxes(&d, 1, cv::cuda::StreamAccessor::getStream(stream)));
+        frame_ = frame; dsize_ = dsize;
+    }
     int maxItems() const { return max_; }
     const void* table() const { return table_.get(); }
     const int32_t* valid() const { return static_cast<const int32_t*>(valid_.get()); } // nullptr when built without

@@ -3,7 +3,7 @@
  * descriptor queue (cvgs_queue_*: an opt-in submission path, frozen since round 5), the device-side arrival flags of the sharded
  * batched-crop path (cvgs_exchange_*: BASELINE cfg #5, SURVEY.md 8e option 2) and plane tables built on the device from a detector's
  * device-side boxes (cvgs_plane_tables_from_boxes) and warp tables fitted on the device to its device-side landmarks
- * (cvgs_warp_tables_from_points), device-side box selection (cvgs_boxes_select), the decoding of a network's raw head into its
+ * (cvgs_warp_tables_from_points) or shaped from its boxes (cvgs_warp_tables_from_boxes), device-side box selection (cvgs_boxes_select), the decoding of a network's raw head into its
  * candidates (cvgs_head_decode) and the gather of the kept candidates' landmarks (cvgs_points_gather).  The drop-in boundary -- what replaces
  * fk::executeOperations and fk::CircularTensor (reference include/cvGPUSpeedup.cuh:464-627) -- is include/cvgs_hip.h alone; nothing
  * there depends on this file.  Same conventions: plain C, asynchronous on the given stream, 0 or a negative cvgs_status.
@@ -269,6 +269,66 @@ typedef struct cvgs_warp_table_desc {
 size_t cvgs_warp_table_bytes(int32_t planes);
 int cvgs_warp_tables_from_points(const cvgs_warp_table_desc* descs, int32_t n, cvgs_stream_t stream);
 int cvgs_warp_table_build_host(const cvgs_warp_table_desc* desc, void* table_out_host);
+
+/* ---- device-built warp tables: context crops from a detector's device-side boxes ---------------------------------------------------------
+ * The read top-down pose, ReID and attribute networks are trained on: grow the detector's box by a context factor, grow its shorter side
+ * to the network's aspect ratio, and sample that rectangle EVEN WHERE IT LEAVES THE FRAME, filling with 0.  The clamped crop
+ * (cvgs_plane_tables_from_boxes) has no margin and squeezes a box at the frame's edge; the warp kernels already render 0 outside the
+ * source.  cvgs_warp_tables_from_boxes enqueues ONE small kernel on `stream` (csrc/k_boxwarp.hip) that turns the boxes of up to
+ * CVGS_WARP_MAX_FRAMES frames into device warp tables (grid y = frame, one work-item per item; the descriptors travel in the kernel
+ * arguments).  Nothing is allocated, staged or synchronised; the launch can be captured between the producer of the boxes (`boxes` /
+ * `count` are exactly cvgs_boxes_select's boxes_out / count_out) and the chains that read the tables.  Its cost: see README.md.
+ *
+ * THE CONTRACT.  One text for the kernel and for cvgs_warp_table_from_boxes_host (csrc/cvgs_geometry.h: box_warp_fit).  Per item,
+ * everything in double, in this order, one rounding per operation, no fma (-ffp-contract=off), correctly rounded division, narrowed to
+ * float at the end, as the landmark fit does:
+ *   1. live = clamp(count ? *count : max_items, 0, max_items); item i >= live is invalid.  The four floats (xa, ya, xb, yb) of a live item --
+ *      EDGE coordinates in frame pixels, xb / yb exclusive -- are widened to double; any non-finite value makes the item invalid.
+ *   2. w = xb - xa; h = yb - ya; invalid unless w > 0 && h > 0.  cx = (xa + xb) * 0.5; cy = (ya + yb) * 0.5.
+ *   3. w1 = w * scale[0]; w1 = w1 + pad[0]; h1 = h * scale[1]; h1 = h1 + pad[1] (the descriptor's floats widened).
+ *   4. CVGS_BOX_SHAPE_EXPAND only: t1 = w1 * (double)dst_height; t2 = h1 * (double)dst_width; if t1 > t2: h1 = t1 / (double)dst_width;
+ *      else if t2 > t1: w1 = t2 / (double)dst_height; equal: unchanged.  The shorter side grows; no rounded ratio of the target's sides
+ *      is ever formed.  CVGS_BOX_SHAPE_STRETCH samples the rectangle of step 3 as it is.
+ *   5. Integer coordinates are pixel centres on both sides (the warp kernels' convention): destination centre u is the edge coordinate
+ *      u + 0.5.  m0 = w1 / (double)dst_width; m4 = h1 / (double)dst_height;
+ *      m2 = (cx - w1 * 0.5) + (m0 * 0.5 - 0.5); m5 = (cy - h1 * 0.5) + (m4 * 0.5 - 0.5); m1 = m3 = 0.
+ *   6. m0, m2, m4, m5 are narrowed to float; any of them not finite: the item is invalid.  A valid entry is the frame's {data, width,
+ *      height, step}, m = {m0, 0, m2, 0, m4, m5, 0, 0, 1}, {dst_width, dst_height} (the same entry for both read kinds); an invalid one
+ *      carries the landmark builder's invalid matrix {0,0,-1, 0,0,-1, 0,0,1}: the plane reads nothing.
+ *   7. boxes_out[i] (optional, device float[max_items][4]): the shaped rectangle in frame EDGE coordinates, NOT clamped, each value
+ *      narrowed from double: (float)(cx - w1*0.5), (float)(cy - h1*0.5), (float)(cx + w1*0.5), (float)(cy + h1*0.5); (0,0,0,0) for an
+ *      invalid item.  It maps second-stage results back to the frame, and is by construction a valid `boxes` of a CVGS_BOX_XYXY_F32
+ *      cvgs_box_table_desc (that call clamps: K1 crops gain the margin too).
+ *   8. valid_out[i] (optional, device int32[max_items]) = 1 / 0.  Every output element is written on every call.
+ * WHY THE TABLE IS SAFE WHATEVER THE DEVICE BUFFER HOLDS: as for the landmark builder -- every entry's frame is the one the HOST validated
+ * here, and the matrix only decides where inside it a plane reads (the warp kernels test 0 <= sx < width && 0 <= sy < height before any tap).
+ * USING THE TABLE: exactly as a table of cvgs_warp_tables_from_points (above), fused warp tick included.
+ * Validation happens completely on the host before the first HIP call: null descriptors or required pointers, struct_size, flags, n
+ * outside 1..16, max_items outside 1..65535, a bad shape, scale not finite or <= 0, pad not finite or < 0, a non-positive target,
+ * misaligned pointers (table_out: 8 bytes; boxes / count / boxes_out / valid_out: 4), a frame that the host lowering would refuse, output
+ * buffers of one call that overlap -> CVGS_ERR_INVALID; non-warp read kinds, CV_64F sources, frames or targets beyond CVGS_MAX_DIM ->
+ * CVGS_ERR_UNSUPPORTED.
+ *   cvgs_warp_table_from_boxes_host  the same descriptor with HOST `boxes` and `count`; desc's output pointers are ignored and the outputs
+ *                                    go to table_out_host (required), boxes_out_host and valid_out_host (either may be NULL).  Runs the
+ *                                    shared text on the CPU and writes the bytes the kernel must write; makes no HIP call.
+ * Rotated boxes, flips, YUV and CV_64F sources and other box formats are not served.  No reference counterpart.                      */
+typedef enum cvgs_box_shape { CVGS_BOX_SHAPE_STRETCH = 0, CVGS_BOX_SHAPE_EXPAND = 1 } cvgs_box_shape;
+typedef struct cvgs_box_warp_desc {
+    uint32_t struct_size, flags;      /* sizeof(cvgs_box_warp_desc); flags: must be 0 */
+    cvgs_image2d frame;               /* the WHOLE frame (device pointer) */
+    int32_t src_type;
+    int32_t read_kind;                /* CVGS_READ_WARP_AFFINE or CVGS_READ_WARP_PERSPECTIVE */
+    int32_t dst_width, dst_height;
+    int32_t shape, max_items;         /* cvgs_box_shape; 1..65535 */
+    float scale[2], pad[2];           /* context factor per axis (x, y): finite, > 0; pixels added per axis: finite, >= 0 */
+    const float* boxes;               /* device: float32 [max_items][4] (xa, ya, xb, yb), edge coordinates in frame pixels */
+    const int32_t* count;             /* device, or NULL */
+    void* table_out;                  /* device, cvgs_warp_table_bytes(max_items) */
+    float* boxes_out;                 /* device float32 [max_items][4], or NULL */
+    int32_t* valid_out;               /* device, or NULL */
+} cvgs_box_warp_desc;
+int cvgs_warp_tables_from_boxes(const cvgs_box_warp_desc* descs, int32_t n, cvgs_stream_t stream); /* n = 1..CVGS_WARP_MAX_FRAMES frames, one call */
+int cvgs_warp_table_from_boxes_host(const cvgs_box_warp_desc* desc, void* table_out_host, float* boxes_out_host, int32_t* valid_out_host);
 
 /* ---- device-side box selection: score threshold, top-K, greedy NMS ---------------------------------------------------------------------
  * What sits between a detector and cvgs_plane_tables_from_boxes.  A detector emits thousands of scored candidates, usually in the
